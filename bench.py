@@ -6,8 +6,20 @@ one full frame: every rank renders its interleaved 8x8 tiles (rtw_render_device)
 all-gather + untile assembles the image on rank 0 (N > 1).  `value` = W*H*spp*steps / max-over-
 ranks wall time of the timed region (strong scaling: the frame is fixed, N GPUs share it).
 
-Extra fields:
-  roofline      the render kernel against its real bound, VALU instruction issue: wave-level VALU
+A plain run (no --full) does only what the headline needs: set-up, the warm-up frames, the --steps
+timed frames (`ms_per_step` = the wall milliseconds one of them took), --dump-outputs, the line.  The
+line's extra fields below are then null (`roofline` keeps the live kernel time and the peak).
+
+--dump-outputs DIR writes what the timed path computed in its last step, after the timed region:
+DIR/image.npy, the frame rank 0 holds (float32, (H, W, 3) linear RGB as the caller of the render
+receives it, but for the few NaN channels the reference's 0/0 pdfs leave: those are 0 there and 1
+in DIR/image_nonfinite.npy, same shape and type, 0 where the channel is finite, 2 / 3 for +inf /
+-inf; frames that would take more than 64 MB in all are cut to a fixed seeded sample of their
+pixels, (n, 3), in pixel order).  The world, the seed and the RNG streams are fixed, so two runs with the same arguments
+write the same array.
+
+Extra fields (--full; each has a --no-... switch):
+  roofline     the render kernel against its real bound, VALU instruction issue: wave-level VALU
                 instructions of one timed frame (rocprofv3 --pmc SQ_INSTS_VALU pass of this same
                 benchmark) / the frame's render-launch time measured live with HIP events on the
                 launch stream, against 256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 VALU
@@ -31,7 +43,7 @@ Extra fields:
                 --configs-steps timed frames (HIP events on the launch stream beside the wall clock),
                 with its own VALU-issue roofline, lane utilisation and HBM traffic from two PMC runs.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (--gpus N > 1 without torchrun: starts N rank processes itself, before any GPU call)
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
@@ -348,6 +360,29 @@ def count_gpus() -> int:
     return n
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir: str, image, width: int, height: int) -> None:
+    """--dump-outputs: the frame the timed path left on the device (a flat W*H*3 float32 tensor, what
+    render_frame() returns) as out_dir/image.npy and image_nonfinite.npy (0 finite, 1 NaN, 2 +inf,
+    3 -inf per channel), both float32 and shaped (H, W, 3); a frame that would take more than
+    DUMP_MAX_BYTES in all as a fixed seeded sample of its pixels in pixel order, shaped (n, 3)."""
+    import numpy as np
+
+    img = image.detach().cpu().numpy().astype(np.float32, copy=False).reshape(height, width, 3)
+    if 2 * img.nbytes > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // 24  # two files of 12 B per pixel
+        pick = np.sort(np.random.default_rng(0x5EED).choice(width * height, size=n, replace=False))
+        img = img.reshape(-1, 3)[pick]
+    # the reference's 0/0 pdfs leave a few NaN channels in a frame (DESIGN P1): the files hold finite
+    # numbers only, so such a channel is 0 in image.npy and named in image_nonfinite.npy
+    code = np.where(np.isnan(img), 1, np.where(np.isposinf(img), 2, np.where(np.isneginf(img), 3, 0)))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "image.npy"), np.ascontiguousarray(np.where(code == 0, img, np.float32(0.0))))
+    np.save(os.path.join(out_dir, "image_nonfinite.npy"), code.astype(np.float32))
+
+
 def launch_ranks(args) -> int:
     """--gpus N > 1 without a launcher: one rank process per GPU, started before this process
     touches the GPU (count_gpus makes no HIP call); rank 0 prints the line."""
@@ -406,6 +441,8 @@ def inproc_bench(args) -> int:
     for _ in range(args.steps):
         mw.render_into(p, img.data_ptr())
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, img, args.width, args.height)
     if args.save:
         from raytracinginaweekend_amd.image_io import save_image
 
@@ -437,6 +474,12 @@ def main() -> int:
     ap.add_argument("--tile", default="8x8", help="partition tile WxH (the headline frame's; a wave takes one tile's pixels)")
     ap.add_argument("--max-depth", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0x5EED)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: first_frame_ms, the roofline's counting render and "
+                         "PMC passes, thread_count, configs, cpu_baseline (each has a --no-... switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed frame as DIR/image.npy, non-finite channels zeroed and named in "
+                         "DIR/image_nonfinite.npy (float32; a seeded pixel sample above 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stats", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC passes (VALU counters, HBM traffic)")
@@ -455,6 +498,9 @@ def main() -> int:
                     help="one process drives the --gpus devices through rtw_multi_render (no ranks, no RCCL)")
     ap.add_argument("--inproc-devices", default="", help="with --inproc: an explicit device list, e.g. 0,0,0")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_stats = args.no_pmc = args.no_first_frame = True
+        args.no_thread_count = args.no_configs = True
 
     if args.inproc:
         return inproc_bench(args)
@@ -512,6 +558,8 @@ def main() -> int:
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(s.elapsed_time(e) for s, e in zip(starts, ends)) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fr.image, args.width, args.height)
 
     if world_size > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)

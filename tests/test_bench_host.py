@@ -24,6 +24,42 @@ def test_count_gpus_reads_kfd_topology_without_hip(tmp_path, monkeypatch):
     assert bench.count_gpus() == 2
 
 
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the size limit whole, as (H, W, 3) float32; a larger one as the
+    same seeded pixel sample on every call, in pixel order and within the limit."""
+    import numpy as np
+    import torch
+
+    w, h = 7, 5
+    flat = torch.arange(w * h * 3, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "a"), flat, w, h)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (h, w, 3)
+    assert np.array_equal(got.ravel(), flat.numpy())
+    code = np.load(tmp_path / "a" / "image_nonfinite.npy")
+    assert code.dtype == np.float32 and code.shape == (h, w, 3) and not code.any()
+
+    # non-finite channels: 0 in the image, named in the code array; every file holds finite numbers only
+    odd = flat.clone()
+    odd[4], odd[17], odd[40] = float("nan"), float("inf"), float("-inf")
+    bench.dump_outputs(str(tmp_path / "n"), odd, w, h)
+    got = np.load(tmp_path / "n" / "image.npy").ravel()
+    code = np.load(tmp_path / "n" / "image_nonfinite.npy").ravel()
+    assert np.isfinite(got).all() and np.isfinite(code).all()
+    assert {int(i): int(code[i]) for i in np.flatnonzero(code)} == {4: 1, 17: 2, 40: 3}
+    assert np.all(got[[4, 17, 40]] == 0) and np.array_equal(got[code == 0], flat.numpy()[code == 0])
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 24)  # room for 10 of the 35 pixels in the two files
+    bench.dump_outputs(str(tmp_path / "b"), flat, w, h)
+    bench.dump_outputs(str(tmp_path / "c"), flat, w, h)
+    s = np.load(tmp_path / "b" / "image.npy")
+    assert s.dtype == np.float32 and s.shape == (10, 3)
+    assert s.nbytes + np.load(tmp_path / "b" / "image_nonfinite.npy").nbytes <= 10 * 24
+    assert np.array_equal(s, np.load(tmp_path / "c" / "image.npy"))
+    pix = s[:, 0] / 3  # channel 0 of pixel p holds 3p
+    assert np.all(np.diff(pix) > 0) and np.array_equal(s, flat.numpy().reshape(-1, 3)[pix.astype(int)])
+
+
 def test_pmc_reduce_takes_the_timed_frame():
     rows = []
     for did, val in [(1, 10.0), (2, 20.0), (3, 30.0), (4, 40.0)]:  # 2 frames x 2 launches

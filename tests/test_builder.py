@@ -10,7 +10,7 @@ import raytracinginaweekend_amd as R
 from oracle import pyref
 from raytracinginaweekend_amd import _native as N
 
-REF_INPUT = "/root/reference/input"
+OBJ_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "obj")  # the reference's input meshes
 
 
 def _world_boxes(world):
@@ -119,10 +119,9 @@ def test_obj_suzanne_counts(assets):
     assert np.all(pos[:, 1] == 0, axis=1).sum() == 500
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INPUT), reason="reference inputs not present")
 @pytest.mark.parametrize("name", ["cube", "suzanne"])
 def test_obj_parser_vs_restatement_on_reference_files(name, assets):
-    text = open(os.path.join(REF_INPUT, f"{name}.obj")).read()
+    text = open(os.path.join(OBJ_DIR, f"{name}.obj")).read()
     got = R.load_obj_mesh(text)
     assert np.array_equal(got, pyref.load_obj(text))
     assert np.array_equal(got, getattr(assets, name))

@@ -40,7 +40,7 @@ for step in "$@"; do
       timeout -k 10 900 python bench.py ${rest//,/ } > $O/bench_$nb.json 2> $O/bench_$nb.err || { tail -20 $O/bench_$nb.err; exit 1; } ;;
     kt)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 bench.py \
-        --no-cpu-baseline --no-pmc --no-configs > $O/kt_bench.json 2> $O/kt.err || exit 1 ;;
+        --full --no-cpu-baseline --no-pmc --no-configs > $O/kt_bench.json 2> $O/kt.err || exit 1 ;;
     part8)
       for s in $(echo ${rest:-final_scene1,suzanne} | tr , ' '); do
         timeout -k 10 300 python tools/part_bench.py --scene $s --parts 8 --ranks all --steps 2 >> $O/part8.txt 2>&1 || exit 1
