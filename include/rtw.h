@@ -306,6 +306,80 @@ RTW_API int rtw_world_last_frame(rtw_gpu_world* gw, int* launches, int* whole_pi
  * `stream` (a hipStream_t, NULL = default stream).  Asynchronous: returns after the launch. */
 RTW_API int rtw_render_device(rtw_gpu_world* gw, const rtw_render_params* params, float* d_out,
                               void* stream);
+/* ---- progressive accumulation ------------------------------------------------------------- */
+/* An accumulator keeps one partition's per-slot running sums of sample colours on the device, so a
+ * frame can grow: add samples in batches, resolve (sum / samples) at any point, export the state
+ * and import it later into an accumulator of the same world, geometry, depth, mode and seed.  A
+ * sample's RNG stream is keyed by (seed, pixel, sample) and the sums are added in sample order, so
+ * after adds of n1, n2, ... samples the resolved image is bit-identical to a one-shot render at
+ * samples_per_pixel = n1 + n2 + ... (and to the reference at that spp).
+ *
+ * The accumulator is tied to one resident world and to params' geometry (width, height, tiles,
+ * part), max_depth, render_mode, seed and layout; params->samples_per_pixel is ignored and may be 0.
+ * params->thread_count > 1 is RTW_ERR_UNSUPPORTED: the reference's plane split depends on the final
+ * spp (split_work_tasks, rendering.rs:222-237), so a prefix of such a frame is not a frame; 0 and 1
+ * are accepted.  The accumulator owns its sums (and squares); the world's own scratch stays the
+ * one-shot frames', so one-shot frames and several accumulators of one world may interleave freely
+ * (they run one at a time, in issue order).  rtw_world_release takes the device state of the world's
+ * live accumulators with it: such an accumulator then refuses every call but rtw_accum_get_info and
+ * rtw_accum_release (a host whose collector frees the two in either order stays safe).
+ *
+ * Work items: where a one-shot frame would take whole-pixel items (rtw_world_last_frame), an
+ * accumulator without moments takes them too (the lane continues the slot's running sum), except
+ * on worlds whose kernel keeps the generic leaf tables in LDS (wrapped, box or volume leaves: the
+ * "true" in the fifth place of rtw_world_kernel_name), which add single samples.  One with
+ * RTW_ACCUM_MOMENTS always takes single-sample items, its squares being summed in the accumulate
+ * pass.  rtw_world_last_frame reports an add like a frame.  DESIGN.md 5.5c. */
+typedef struct rtw_accum rtw_accum;
+#define RTW_ACCUM_MOMENTS 1u /* also keep per-channel sums of squares (the noise estimate) */
+typedef struct rtw_accum_info { /* all fields fixed-width, no padding; also the checkpoint header */
+    uint32_t version; /* 1 */
+    uint32_t flags;   /* RTW_ACCUM_* */
+    int32_t width, height, tile_width, tile_height, part_index, part_count;
+    int32_t max_depth, render_mode;
+    uint32_t samples;  /* samples added so far, per pixel */
+    uint32_t reserved; /* 0 */
+    uint64_t seed;
+    uint64_t world_fingerprint; /* rtw_world_fingerprint of the uploaded world */
+    int64_t slots;              /* floats per state array = 3 * slots */
+} rtw_accum_info;
+
+/* 64-bit FNV-1a over the world's contents in declaration order: camera, background, has_light,
+ * light, root; every count followed by its table's bytes; per image its width, height and pixels.
+ * Pointers are not hashed.  Host only.  rtw_world_upload stores it in the rtw_gpu_world. */
+RTW_API int rtw_world_fingerprint(const rtw_world* w, uint64_t* out);
+RTW_API int rtw_accum_create(rtw_gpu_world* gw, const rtw_render_params* params, uint32_t flags,
+                             rtw_accum** out);
+RTW_API int rtw_accum_release(rtw_accum* a);
+/* Renders samples [samples, samples + n) of every slot and adds their colours to the running sums
+ * in sample order (with RTW_ACCUM_MOMENTS also sq = sq + c * c per channel, product and sum each
+ * rounded to f32).  Asynchronous on `stream`; one add may be several launches (colour-buffer
+ * budget, RTW_CHUNK).  n == 0 does nothing; samples + n beyond 32 bits is
+ * RTW_ERR_INVALID_ARGUMENT. */
+RTW_API int rtw_accum_add(rtw_accum* a, uint32_t n_samples, void* stream);
+RTW_API int rtw_accum_get_info(rtw_accum* a, rtw_accum_info* out); /* host bookkeeping, no sync */
+/* sum / (float)samples into device buffer d_out, in params->layout.  Non-destructive; needs
+ * samples >= 1.  Asynchronous. */
+RTW_API int rtw_accum_resolve(rtw_accum* a, float* d_out, void* stream);
+/* The standard error of the mean per channel (needs RTW_ACCUM_MOMENTS and samples >= 2), in f32:
+ * nf = (float)samples; mean = sum / nf; d = sq - sum * mean; var = (d < 0 ? 0 : d) / (float)(samples - 1);
+ * se = sqrt(var / nf).  Same layout as the resolve.  Asynchronous. */
+RTW_API int rtw_accum_resolve_stderr(rtw_accum* a, float* d_out, void* stream);
+/* One scalar for the partition: the f64 mean over its pixels of the f32 value
+ * e = ((se_r + se_g) + se_b) / (((mean_r + mean_g) + mean_b) + 0.01f), leaving out pixels whose e is
+ * not finite; *pixels_counted = pixels that entered the mean (0: *noise = 0).  Same conditions as the
+ * stderr.  Synchronous. */
+RTW_API int rtw_accum_noise(rtw_accum* a, void* stream, double* noise, int64_t* pixels_counted);
+/* Copies the sums (and, with moments, the squares; host_squares may be NULL otherwise) to the host,
+ * 3 * slots floats each, in slot order (tile-major); padding slots of edge tiles hold zeros.
+ * Synchronous. */
+RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares);
+/* Sets the sums (and squares) and the sample count from an exported state.  `info` must match the
+ * accumulator's own version, flags, geometry, max_depth, render_mode, seed, world fingerprint and
+ * slots, else RTW_ERR_INVALID_ARGUMENT with a message naming the field.  Synchronous. */
+RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                             const float* host_squares);
+
 /* Floats needed by one partition's RTW_LAYOUT_TILES buffer (tiles * tile_w * tile_h * 3). */
 RTW_API int rtw_partition_floats(const rtw_render_params* params, int64_t* floats);
 /* Scatters part_count gathered tile buffers (each padded to `stride_floats`) into a W*H*3

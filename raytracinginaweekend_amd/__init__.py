@@ -6,6 +6,13 @@ include/rtw.h).  This package is its Python face, mirroring the reference's inte
 Camera.build()..., WorldBuilder / NodeBuilder, demo worlds, rendering.render(...).
 """
 from . import image_io
+from .progressive import (
+    Accumulator,
+    AccumState,
+    render_progressive,
+    render_to_noise,
+    world_fingerprint,
+)
 from .rendering import (
     DeviceWorld,
     MultiDeviceWorld,
@@ -31,6 +38,8 @@ from .world import (
 )
 
 __all__ = [
+    "AccumState",
+    "Accumulator",
     "AssetSet",
     "BackgroundColor",
     "Camera",
@@ -50,4 +59,7 @@ __all__ = [
     "render",
     "render_devices",
     "render_params",
+    "render_progressive",
+    "render_to_noise",
+    "world_fingerprint",
 ]

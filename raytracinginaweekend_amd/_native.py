@@ -190,6 +190,29 @@ class RenderStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+ACCUM_MOMENTS = 1  # RTW_ACCUM_MOMENTS
+
+
+class AccumInfo(C.Structure):  # rtw_accum_info: fixed-width fields, no padding (also the checkpoint header)
+    _fields_ = [
+        ("version", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("tile_width", C.c_int32),
+        ("tile_height", C.c_int32),
+        ("part_index", C.c_int32),
+        ("part_count", C.c_int32),
+        ("max_depth", C.c_int32),
+        ("render_mode", C.c_int32),
+        ("samples", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("world_fingerprint", C.c_uint64),
+        ("slots", C.c_int64),
+    ]
+
+
 class CameraSpec(C.Structure):
     _fields_ = [
         ("fov_mode", C.c_int32),
@@ -252,6 +275,16 @@ _SIGS = {
     "rtw_multi_render": (C.c_int, [_P, C.POINTER(RenderParams), _P]),
     "rtw_multi_release": (C.c_int, [_P]),
     "rtw_multi_peer_copies": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "rtw_world_fingerprint": (C.c_int, [C.POINTER(World), C.POINTER(C.c_uint64)]),
+    "rtw_accum_create": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.POINTER(_P)]),
+    "rtw_accum_release": (C.c_int, [_P]),
+    "rtw_accum_add": (C.c_int, [_P, C.c_uint32, _P]),
+    "rtw_accum_get_info": (C.c_int, [_P, C.POINTER(AccumInfo)]),
+    "rtw_accum_resolve": (C.c_int, [_P, _P, _P]),
+    "rtw_accum_resolve_stderr": (C.c_int, [_P, _P, _P]),
+    "rtw_accum_noise": (C.c_int, [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "rtw_accum_export": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "rtw_accum_import": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "rtw_partition_floats": (C.c_int, [C.POINTER(RenderParams), C.POINTER(C.c_int64)]),
     "rtw_untile_device": (C.c_int, [C.POINTER(RenderParams), _P, C.c_int64, _P, _P]),
     "rtw_render_collect_stats": (C.c_int, [_P, C.POINTER(RenderParams), C.POINTER(RenderStats)]),

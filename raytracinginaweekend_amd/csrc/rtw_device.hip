@@ -229,7 +229,11 @@ struct KArgs {
     uint64_t tune_items;      // items per tuning epoch (0: this launch does not explore)
     // 1: a work item is a whole pixel (all spp samples of a slot, one lane, in sample order): the lane
     // sums the colours in registers -- the reference's sequential .sum(), rendering.rs:172-179 -- and
-    // writes sum / spp to `out` itself; no colour buffer, no accumulation kernel (thread_count 1)
+    // writes sum / spp to `out` itself; no colour buffer, no accumulation kernel (thread_count 1).
+    // An accumulator's add (rtw_accum_add) with such items passes its own sums as `out` in the tile
+    // layout with spp = 1: the lane stores its sum undivided (x / 1 is x), and a launch with s_begin > 0
+    // -- a one-shot whole-pixel frame is one launch from sample 0 -- starts each pixel from out[slot]
+    // (render_kernel's WP = true variants; worlds that take a GEN kernel add single samples instead)
     int32_t whole_pixel;
     // work order by measured cost (render_frame): costlier tiles first, all their samples together
     const uint32_t* tile_perm;  // tile rank -> local tile, null: chunk-major order
@@ -2468,6 +2472,12 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                         sample = big ? A.s_begin + ck * A.chunk : A.s_split + ck;
                         sample_end = big ? min(sample + A.chunk, A.s_split) : sample + 1;
                         psum = v3(0.0f, 0.0f, 0.0f);
+                        // (the WP = true kernels only: in the GEN kernels, which take whole-pixel items at run
+                        // time, these lines moved the SGPR spills of every frame -- profiles/r07/resources_accum.txt)
+                        if (WP && A.s_begin != 0) {  // wave-uniform: an accumulator's add continues its sum
+                            const float* r = A.out + 3 * (size_t)slot;  // (KArgs::whole_pixel)
+                            psum = v3(r[0], r[1], r[2]);
+                        }
                         pcost = 0;
                         start_sample(1);
                         T.phase = PH_TRACE;
@@ -2867,6 +2877,114 @@ __global__ void accumulate_kernel(const float* __restrict__ colors, uint32_t n_s
         running[3 * (size_t)slot] = sum.x;
         running[3 * (size_t)slot + 1] = sum.y;
         running[3 * (size_t)slot + 2] = sum.z;
+    }
+}
+
+// ---- progressive accumulation (rtw_accum) ----------------------------------------
+// A slot's pixel in its partition (false: padding slot of an edge tile, or past the partition).
+struct SlotGeom {
+    uint32_t total;
+    int32_t width, height, tile_w, tile_h, tiles_x, part_index, part_count;
+};
+__device__ __forceinline__ bool slot_pixel(const SlotGeom& G, uint32_t slot, int32_t& px, int32_t& py) {
+    if (slot >= G.total) return false;
+    const int32_t per_tile = G.tile_w * G.tile_h;
+    const int32_t tile = G.part_index + (int32_t)(slot / (uint32_t)per_tile) * G.part_count;
+    const int32_t it = (int32_t)(slot % (uint32_t)per_tile);
+    px = (tile % G.tiles_x) * G.tile_w + it % G.tile_w;
+    py = (tile / G.tiles_x) * G.tile_h + it / G.tile_w;
+    return px < G.width && py < G.height;
+}
+// An accumulator's add with RTW_ACCUM_MOMENTS: accumulate_kernel's in-order sum onto the accumulator's
+// own running sum, and per channel sq = add(sq, mul(c, c)) (two roundings: no contraction in this build).
+__global__ void accumulate_moments_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G,
+                                          float* __restrict__ sums, float* __restrict__ squares) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    if (!slot_pixel(G, slot, px, py)) return;
+    float* S = sums + 3 * (size_t)slot;
+    float* Q = squares + 3 * (size_t)slot;
+    V3 sum = v3(S[0], S[1], S[2]), sq = v3(Q[0], Q[1], Q[2]);
+    const float* c = colors + 3 * (size_t)slot;
+    for (uint32_t s = 0; s < n_samples; ++s, c += 3 * (size_t)G.total) {
+        const V3 col = v3(c[0], c[1], c[2]);
+        sum = add(sum, col);
+        sq = add(sq, conv(col, col));
+    }
+    S[0] = sum.x;
+    S[1] = sum.y;
+    S[2] = sum.z;
+    Q[0] = sq.x;
+    Q[1] = sq.y;
+    Q[2] = sq.z;
+}
+// the standard error of a channel's mean from its sum and sum of squares (rtw.h: the order is the contract)
+__device__ __forceinline__ float accum_se(float sum, float sq, uint32_t samples, float& mean) {
+    const float nf = (float)samples;
+    mean = sum / nf;
+    const float d = sq - sum * mean;
+    const float var = (d < 0.0f ? 0.0f : d) / (float)(samples - 1);  // a NaN d stays NaN
+    return __builtin_sqrtf(var / nf);
+}
+// what 0: sum / samples (accumulate_kernel's last step); 1: the standard error (needs squares)
+__global__ void accum_resolve_kernel(const float* __restrict__ sums, const float* __restrict__ squares, SlotGeom G,
+                                     uint32_t samples, int what, float* out, int layout) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    if (!slot_pixel(G, slot, px, py)) return;
+    const float* S = sums + 3 * (size_t)slot;
+    V3 r;
+    if (what == 0) {
+        r = divs(v3(S[0], S[1], S[2]), (float)samples);
+    } else {
+        const float* Q = squares + 3 * (size_t)slot;
+        float m;
+        r = v3(accum_se(S[0], Q[0], samples, m), accum_se(S[1], Q[1], samples, m), accum_se(S[2], Q[2], samples, m));
+    }
+    float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
+    o[0] = r.x;
+    o[1] = r.y;
+    o[2] = r.z;
+}
+// rtw_accum_noise: per block the f64 sum of the finite per-pixel relative errors and their count, reduced
+// in a fixed tree order (the host adds the blocks in block order)
+#define RTW_NOISE_BLOCK 256
+__global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const float* __restrict__ sums,
+                                                                      const float* __restrict__ squares, SlotGeom G,
+                                                                      uint32_t samples, double* __restrict__ part_sum,
+                                                                      uint32_t* __restrict__ part_count) {
+    __shared__ double sh_sum[RTW_NOISE_BLOCK];
+    __shared__ uint32_t sh_cnt[RTW_NOISE_BLOCK];
+    const uint32_t slot = blockIdx.x * RTW_NOISE_BLOCK + threadIdx.x;
+    double v = 0.0;
+    uint32_t n = 0;
+    int32_t px, py;
+    if (slot_pixel(G, slot, px, py)) {
+        const float* S = sums + 3 * (size_t)slot;
+        const float* Q = squares + 3 * (size_t)slot;
+        float mr, mg, mb;
+        const float sr = accum_se(S[0], Q[0], samples, mr);
+        const float sg = accum_se(S[1], Q[1], samples, mg);
+        const float sb = accum_se(S[2], Q[2], samples, mb);
+        const float e = ((sr + sg) + sb) / (((mr + mg) + mb) + 0.01f);
+        if (__builtin_fabsf(e) < F32_INF) {  // finite (false for NaN)
+            v = (double)e;
+            n = 1;
+        }
+    }
+    sh_sum[threadIdx.x] = v;
+    sh_cnt[threadIdx.x] = n;
+    __syncthreads();
+    for (int step = RTW_NOISE_BLOCK / 2; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step) {
+            sh_sum[threadIdx.x] += sh_sum[threadIdx.x + step];
+            sh_cnt[threadIdx.x] += sh_cnt[threadIdx.x + step];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part_sum[blockIdx.x] = sh_sum[0];
+        part_count[blockIdx.x] = sh_cnt[0];
     }
 }
 
@@ -3594,6 +3712,8 @@ struct rtw_gpu_world {
     int32_t last_kernel[6] = {-1, -1, -1, -1, -1, -1};
     // the last frame: render launches, whole-pixel items, the default threshold, in-frame tuning on
     int32_t last_frame[4] = {-1, -1, -1, 0};
+    uint64_t fingerprint = 0;  // rtw_world_fingerprint of the uploaded world (accumulator checkpoints)
+    std::vector<struct rtw_accum*> accums;  // live accumulators: rtw_world_release orphans them (accum_orphan)
 };
 
 // experiment builds (-DRTW_WAVE_TIMING): per-wave start / end / queue-empty wall clocks (100 MHz) of
@@ -3837,6 +3957,7 @@ extern "C" RTW_API int rtw_world_upload(const rtw_world* w, int device, rtw_gpu_
     const size_t o_dw = L.push(&dw_zero, sizeof(DWorld));  // filled once the pointers are known
 
     auto* g = new rtw_gpu_world;
+    (void)rtw_world_fingerprint(w, &g->fingerprint);  // (check_world passed: every table is there)
     g->device = device;
     hipError_t e = hipMalloc(&g->arena, L.blob.size());
     if (e != hipSuccess) {
@@ -4103,9 +4224,12 @@ extern "C" RTW_API int rtw_world_last_frame(rtw_gpu_world* g, int* launches, int
     return RTW_OK;
 }
 
+static void accum_orphan(struct rtw_accum* a);
+
 extern "C" RTW_API int rtw_world_release(rtw_gpu_world* g) {
     if (!g) return RTW_OK;
     (void)hipSetDevice(g->device);
+    for (struct rtw_accum* a : g->accums) accum_orphan(a);
     if (g->arena) (void)hipFree(g->arena);
     if (g->queue) (void)hipFree(g->queue);
     if (g->colors) (void)hipFree(g->colors);
@@ -4181,7 +4305,10 @@ int make_args(const rtw_gpu_world* g, const rtw_render_params* p, KArgs& A) {
 // fits, size the grid to the resident block count.
 enum LaunchKind { LK_RENDER, LK_STATS };
 size_t env_size(const char* name, size_t dflt);
-int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream) {
+// acc_wp: an accumulator's add with whole-pixel items (KArgs::whole_pixel); RTW_ACC_NO_WP, before anything is
+// launched, when the world takes a GEN kernel, whose whole-pixel code cannot continue a sum
+constexpr int RTW_ACC_NO_WP = -1;
+int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool acc_wp = false) {
     const bool stats = kind == LK_STATS;
     const bool ktree = stats && A.stats_tree == 1;  // count the product kernel's own traversal
     // the leaf and texture kinds the world needs; RTW_LEAF_KINDS=4 / RTW_TEX_KINDS=1 force the
@@ -4330,6 +4457,7 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream) {
     const bool gen = !stats && A.sh_xf >= 0;  // (the counting variant reads the HBM copies)
     if (gen && tx != TX_SOLID && A.sh_tex0 >= 0)  // those kernels compile no LDS texture path (texture_sample)
         return rtw::fail(RTW_ERR_UNSUPPORTED, "GEN kernel with a texture table in LDS");
+    if (gen && acc_wp) return RTW_ACC_NO_WP;
     const int wp = A.whole_pixel ? 1 : 0;  // (never in the counting variant, render_frame_body)
     const KFn kf = stats ? (sah ? fns_stats_sah[lk][mode] : fns_stats[mode])
                  : gen   ? fns_gen[tx][lk - LK_WRAPPED][mode - 1]
@@ -4427,23 +4555,35 @@ int grow(void** buf, size_t* have, size_t need) {
 // each followed by the in-order accumulation; work items of RTW_CHUNK (default 1) samples.
 // Launch l of a frame takes its work items from queue block min(l, RTW_QUEUE_SLOTS - 1) of the
 // world's counters, so a progress poller can read how many items each launch has handed out.
+// An accumulator's add (rtw_accum_add) runs through the same body: samples [base, base + A.spp) onto
+// the accumulator's own sums (and squares), no final division, nothing of the world's running buffer.
+struct AccumRun {
+    float* sums;
+    float* squares;  // null: no moments
+    uint32_t base;   // samples the sums already hold
+};
 int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStream_t stream,
-                      std::vector<uint64_t>* launch_items);
+                      std::vector<uint64_t>* launch_items, const AccumRun* acc, bool acc_allow_wp = true);
 
 // One render at a time per world: a frame reuses the world's queue, colour, running-sum and
 // cost buffers, so a frame issued on another stream first waits for the previous frame's end.
 int render_frame(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStream_t stream,
-                 std::vector<uint64_t>* launch_items = nullptr) {
+                 std::vector<uint64_t>* launch_items = nullptr, const AccumRun* acc = nullptr) {
     if (!g->done) HIP_TRY(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
     if (g->done_recorded) HIP_TRY(hipStreamWaitEvent(stream, g->done, 0));
-    const int rc = render_frame_body(g, A, stats, out, stream, launch_items);
+    const KArgs A0 = A;
+    int rc = render_frame_body(g, A, stats, out, stream, launch_items, acc);
+    if (rc == RTW_ACC_NO_WP) {  // (nothing was launched) the same add with single-sample items
+        A = A0;
+        rc = render_frame_body(g, A, stats, out, stream, launch_items, acc, false);
+    }
     HIP_TRY(hipEventRecord(g->done, stream));
     g->done_recorded = true;
     return rc;
 }
 
 int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStream_t stream,
-                      std::vector<uint64_t>* launch_items) {
+                      std::vector<uint64_t>* launch_items, const AccumRun* acc, bool acc_allow_wp) {
     if (A.total == 0) return RTW_OK;
     // Whole-pixel items (KArgs::whole_pixel): thread_count 1 only (the planes' merge needs every
     // plane's value), never in the counting variant; RTW_WHOLE_PIXEL=1 selects them (A/B runs)
@@ -4453,7 +4593,10 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
     // profiles/r04/v2_experiments_ab.txt).  With few pixels per lane (an 8-GPU share of C5: 4) single-
     // sample items balance the lanes.  RTW_WHOLE_PIXEL=1 / 0 forces them on / off.
     A.whole_pixel = 0;
-    if (!stats && A.thread_count <= 1) {
+    // An accumulator that keeps moments always takes single-sample items: the squares are summed in the
+    // accumulate pass, so the render kernel holds no extra registers for them
+    // (... nor one whose world takes a GEN kernel: launch_render's RTW_ACC_NO_WP, render_frame)
+    if (!stats && A.thread_count <= 1 && !(acc && (acc->squares || !acc_allow_wp))) {
         const uint64_t lanes = (uint64_t)std::max(1, g->cus) * RTW_BLOCK;
         const char* wp = std::getenv("RTW_WHOLE_PIXEL");
         if (wp && wp[0] == '1') A.whole_pixel = 1;
@@ -4496,7 +4639,7 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
     if (plane_buffer) {
         rc = grow((void**)&g->running, &g->running_bytes, per_sample * n_planes);
         if (rc != RTW_OK) return rc;
-    } else if (n_planes <= 1 && per_launch < A.spp) {
+    } else if (n_planes <= 1 && per_launch < A.spp && !acc) {
         rc = grow((void**)&g->running, &g->running_bytes, per_sample);
         if (rc != RTW_OK) return rc;
     }
@@ -4530,7 +4673,7 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
     const char* nr = std::getenv("RTW_NO_REORDER");
     if (!stats && !(nr && nr[0] && nr[0] != '0')) {
         const uint64_t key[10] = {A.total, (uint64_t)A.part_index, (uint64_t)A.part_count, (uint64_t)A.tiles_x,
-                                  (uint64_t)A.tile_w, (uint64_t)A.tile_h, A.seed_key, A.spp, (uint64_t)(uint32_t)A.max_depth,
+                                  (uint64_t)A.tile_w, (uint64_t)A.tile_h, A.seed_key, acc ? 0u : A.spp, (uint64_t)(uint32_t)A.max_depth,
                                   (uint64_t)(uint32_t)A.mode};
         if (std::memcmp(key, g->order_key, sizeof(key)) != 0 || !g->slot_cost) {
             if (g->slot_cost) (void)hipFree(g->slot_cost);
@@ -4557,16 +4700,34 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
     int launch = 0;
     for (uint32_t s0 = 0; s0 < A.spp; s0 += (uint32_t)per_launch, ++launch) {
         const uint32_t s1 = (uint32_t)std::min<uint64_t>(A.spp, s0 + per_launch);
-        A.s_begin = s0;
-        A.s_end = s1;
+        // (an accumulator's samples continue where its sums stand: the RNG streams are keyed by sample)
+        A.s_begin = (acc ? acc->base : 0u) + s0;
+        A.s_end = (acc ? acc->base : 0u) + s1;
         set_items(A, chunk);
         A.queue = g->queue + (size_t)std::min(launch, RTW_QUEUE_SLOTS - 1) * RTW_QUEUE_BLOCK;
         if (launch_items) launch_items->push_back(A.items);
-        rc = launch_render(g, A, stats ? LK_STATS : LK_RENDER, stream);
+        if (acc && A.whole_pixel) {  // the lanes continue the accumulator's sums (KArgs::whole_pixel)
+            KArgs B = A;
+            B.spp = 1;
+            B.out = acc->sums;
+            B.layout = RTW_LAYOUT_TILES;
+            rc = launch_render(g, B, LK_RENDER, stream, true);
+            if (rc == RTW_ACC_NO_WP && launch_items) launch_items->pop_back();
+        } else {
+            rc = launch_render(g, A, stats ? LK_STATS : LK_RENDER, stream);
+        }
         if (rc != RTW_OK) return rc;
         const unsigned blocks = (A.total + 255) / 256;
         if (A.whole_pixel) {
             // the render kernel wrote the pixels
+        } else if (acc && acc->squares) {
+            const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
+            hipLaunchKernelGGL(accumulate_moments_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
+                               s1 - s0, G, acc->sums, acc->squares);
+        } else if (acc) {  // the one-shot frames' kernel as a middle launch: onto the sums, no division
+            hipLaunchKernelGGL(accumulate_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors, s1 - s0,
+                               A.total, acc->sums, 0, 0, A.spp, out, A.layout, A.width, A.height, A.tile_w, A.tile_h,
+                               A.tiles_x, A.part_index, A.part_count);
         } else if (n_planes > 1 && !plane_buffer)
             hipLaunchKernelGGL(merge_planes_direct_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
                                A.total, n_planes, whole, rem, out, A.layout, A.width, A.height, A.tile_w, A.tile_h,
@@ -4623,6 +4784,258 @@ extern "C" RTW_API int rtw_render_device(rtw_gpu_world* g, const rtw_render_para
     A.out = d_out;
     HIP_TRY(hipSetDevice(g->device));
     return render_frame(g, A, false, d_out, (hipStream_t)stream);
+}
+
+// ---- progressive accumulation (rtw.h) --------------------------------------------
+struct rtw_accum {
+    rtw_gpu_world* g = nullptr;
+    rtw_render_params p{};  // samples_per_pixel: set per add
+    rtw_accum_info info{};
+    float* sums = nullptr;     // 3 floats per slot, owned; padding slots stay zero
+    float* squares = nullptr;  // the same with RTW_ACCUM_MOMENTS, else null
+    double* noise_sum = nullptr;  // rtw_accum_noise: per-block partials (device), grown on first use
+    uint32_t* noise_cnt = nullptr;
+};
+
+// The world went first (rtw_world_release): the accumulator's device state goes with it, and every later
+// call on it but rtw_accum_get_info and rtw_accum_release is refused.
+static void accum_orphan(rtw_accum* a) {
+    if (a->sums) (void)hipFree(a->sums);
+    if (a->squares) (void)hipFree(a->squares);
+    if (a->noise_sum) (void)hipFree(a->noise_sum);
+    if (a->noise_cnt) (void)hipFree(a->noise_cnt);
+    a->sums = a->squares = nullptr;
+    a->noise_sum = nullptr;
+    a->noise_cnt = nullptr;
+    a->g = nullptr;
+}
+
+namespace {
+SlotGeom accum_geom(const KArgs& A) {
+    return SlotGeom{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
+}
+// the accumulator's launch arguments for `spp` samples (geometry checks as for a one-shot frame)
+int accum_args(const rtw_accum* a, uint32_t spp, KArgs& A) {
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    rtw_render_params q = a->p;
+    q.samples_per_pixel = spp;
+    return make_args(a->g, &q, A);
+}
+// The world's frames and its accumulators' calls run one at a time in issue order (render_frame's `done`
+// event): a call on `stream` first waits for the last one, and is itself the next one to wait for.
+int accum_enter(rtw_accum* a, hipStream_t stream) {
+    rtw_gpu_world* g = a->g;
+    HIP_TRY(hipSetDevice(g->device));
+    if (!g->done) HIP_TRY(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
+    if (g->done_recorded) HIP_TRY(hipStreamWaitEvent(stream, g->done, 0));
+    return RTW_OK;
+}
+int accum_leave(rtw_accum* a, hipStream_t stream) {
+    HIP_TRY(hipEventRecord(a->g->done, stream));
+    a->g->done_recorded = true;
+    return RTW_OK;
+}
+int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
+    if (!a || !d_out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (what == 0 && a->info.samples < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "resolve needs samples >= 1");
+    if (what == 1 && !a->squares)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs an accumulator with RTW_ACCUM_MOMENTS");
+    if (what == 1 && a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs samples >= 2");
+    KArgs A;
+    int rc = accum_args(a, 1, A);
+    if (rc != RTW_OK) return rc;
+    if (A.total == 0) return RTW_OK;
+    rc = accum_enter(a, stream);
+    if (rc != RTW_OK) return rc;
+    hipLaunchKernelGGL(accum_resolve_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream, (const float*)a->sums,
+                       (const float*)a->squares, accum_geom(A), a->info.samples, what, d_out, A.layout);
+    HIP_TRY(hipGetLastError());
+    return accum_leave(a, stream);
+}
+}  // namespace
+
+extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t flags, rtw_accum** out) {
+    if (!g || !p || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (flags & ~RTW_ACCUM_MOMENTS) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown accumulator flags");
+    if (p->thread_count > 1)
+        return rtw::fail(RTW_ERR_UNSUPPORTED,
+                         "accumulators take thread_count 0 or 1: the reference's plane split depends on the final "
+                         "samples_per_pixel, so a prefix of such a frame is not a frame");
+    if (p->layout != RTW_LAYOUT_IMAGE && p->layout != RTW_LAYOUT_TILES)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown layout");
+    auto* a = new rtw_accum;
+    a->g = g;
+    a->p = *p;
+    KArgs A;
+    const int rc = accum_args(a, 1, A);
+    if (rc != RTW_OK) {
+        delete a;
+        return rc;
+    }
+    rtw_accum_info& I = a->info;
+    I.version = 1;
+    I.flags = flags;
+    I.width = A.width;
+    I.height = A.height;
+    I.tile_width = A.tile_w;
+    I.tile_height = A.tile_h;
+    I.part_index = A.part_index;
+    I.part_count = A.part_count;
+    I.max_depth = p->max_depth;
+    I.render_mode = p->render_mode;
+    I.samples = 0;
+    I.reserved = 0;
+    I.seed = p->seed;
+    I.world_fingerprint = g->fingerprint;
+    I.slots = (int64_t)A.total;
+    (void)hipSetDevice(g->device);
+    const size_t bytes = std::max<size_t>(16, (size_t)A.total * 3 * sizeof(float));
+    hipError_t e = hipMalloc(&a->sums, bytes);
+    if (e == hipSuccess && (flags & RTW_ACCUM_MOMENTS)) e = hipMalloc(&a->squares, bytes);
+    if (e != hipSuccess) {
+        rtw_accum_release(a);
+        return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    // (synchronous: the zeros are there before any stream's first add)
+    e = hipMemset(a->sums, 0, bytes);
+    if (e == hipSuccess && a->squares) e = hipMemset(a->squares, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        rtw_accum_release(a);
+        return rtw::fail(RTW_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e));
+    }
+    g->accums.push_back(a);
+    *out = a;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_release(rtw_accum* a) {
+    if (!a) return RTW_OK;
+    if (rtw_gpu_world* g = a->g) {  // (else rtw_world_release freed the device state)
+        (void)hipSetDevice(g->device);
+        g->accums.erase(std::remove(g->accums.begin(), g->accums.end(), a), g->accums.end());
+        accum_orphan(a);
+    }
+    delete a;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_get_info(rtw_accum* a, rtw_accum_info* out) {
+    if (!a || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    *out = a->info;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_add(rtw_accum* a, uint32_t n, void* stream) {
+    if (!a) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return RTW_OK;
+    if ((uint64_t)a->info.samples + n > 0xFFFFFFFFull)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's sample count would pass 32 bits");
+    KArgs A;
+    const int v = accum_args(a, n, A);
+    if (v != RTW_OK) return v;
+    A.out = nullptr;  // an add writes the accumulator's state only
+    HIP_TRY(hipSetDevice(a->g->device));
+    const AccumRun run{a->sums, a->squares, a->info.samples};
+    const int rc = render_frame(a->g, A, false, nullptr, (hipStream_t)stream, nullptr, &run);
+    if (rc != RTW_OK) return rc;
+    a->info.samples += n;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_resolve(rtw_accum* a, float* d_out, void* stream) {
+    return accum_resolve(a, d_out, (hipStream_t)stream, 0);
+}
+
+extern "C" RTW_API int rtw_accum_resolve_stderr(rtw_accum* a, float* d_out, void* stream) {
+    return accum_resolve(a, d_out, (hipStream_t)stream, 1);
+}
+
+extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* noise, int64_t* pixels_counted) {
+    if (!a || !noise || !pixels_counted) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (!a->squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the noise estimate needs an accumulator with RTW_ACCUM_MOMENTS");
+    if (a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the noise estimate needs samples >= 2");
+    hipStream_t stream = (hipStream_t)stream_;
+    KArgs A;
+    int rc = accum_args(a, 1, A);
+    if (rc != RTW_OK) return rc;
+    *noise = 0.0;
+    *pixels_counted = 0;
+    if (A.total == 0) return RTW_OK;
+    rc = accum_enter(a, stream);
+    if (rc != RTW_OK) return rc;
+    const uint32_t blocks = (A.total + RTW_NOISE_BLOCK - 1) / RTW_NOISE_BLOCK;
+    if (!a->noise_sum) {
+        HIP_TRY(hipMalloc(&a->noise_sum, (size_t)blocks * sizeof(double)));
+        HIP_TRY(hipMalloc(&a->noise_cnt, (size_t)blocks * sizeof(uint32_t)));
+    }
+    hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, (const float*)a->sums,
+                       (const float*)a->squares, accum_geom(A), a->info.samples, a->noise_sum, a->noise_cnt);
+    HIP_TRY(hipGetLastError());
+    rc = accum_leave(a, stream);
+    if (rc != RTW_OK) return rc;
+    std::vector<double> hs(blocks);
+    std::vector<uint32_t> hc(blocks);
+    HIP_TRY(hipMemcpyAsync(hs.data(), a->noise_sum, (size_t)blocks * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(hc.data(), a->noise_cnt, (size_t)blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    double sum = 0.0;
+    int64_t count = 0;
+    for (uint32_t b = 0; b < blocks; ++b) {  // in block order
+        sum += hs[b];
+        count += hc[b];
+    }
+    *pixels_counted = count;
+    *noise = count > 0 ? sum / (double)count : 0.0;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares) {
+    if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
+    HIP_TRY(hipSetDevice(a->g->device));
+    if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
+    const size_t bytes = (size_t)a->info.slots * 3 * sizeof(float);
+    if (bytes == 0) return RTW_OK;
+    HIP_TRY(hipMemcpy(host_sums, a->sums, bytes, hipMemcpyDeviceToHost));
+    if (a->squares) HIP_TRY(hipMemcpy(host_squares, a->squares, bytes, hipMemcpyDeviceToHost));
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                        const float* host_squares) {
+    if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    const rtw_accum_info& M = a->info;
+    auto differs = [](const char* field) {
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("checkpoint does not match the accumulator: ") + field + " differs");
+    };
+    if (info->version != M.version) return differs("version");
+    if (info->flags != M.flags) return differs("flags");
+    if (info->width != M.width) return differs("width");
+    if (info->height != M.height) return differs("height");
+    if (info->tile_width != M.tile_width) return differs("tile_width");
+    if (info->tile_height != M.tile_height) return differs("tile_height");
+    if (info->part_index != M.part_index) return differs("part_index");
+    if (info->part_count != M.part_count) return differs("part_count");
+    if (info->max_depth != M.max_depth) return differs("max_depth");
+    if (info->render_mode != M.render_mode) return differs("render_mode");
+    if (info->seed != M.seed) return differs("seed");
+    if (info->world_fingerprint != M.world_fingerprint) return differs("world_fingerprint");
+    if (info->slots != M.slots) return differs("slots");
+    if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
+    HIP_TRY(hipSetDevice(a->g->device));
+    if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
+    const size_t bytes = (size_t)M.slots * 3 * sizeof(float);
+    if (bytes > 0) {
+        HIP_TRY(hipMemcpy(a->sums, host_sums, bytes, hipMemcpyHostToDevice));
+        if (a->squares) HIP_TRY(hipMemcpy(a->squares, host_squares, bytes, hipMemcpyHostToDevice));
+    }
+    a->info.samples = info->samples;
+    return RTW_OK;
 }
 
 namespace {
