@@ -302,6 +302,21 @@ RTW_API int rtw_world_kernel_name(rtw_gpu_world* gw, char* buf, int cap);
  * world's tuned one once chosen, else the default: 32, 16 for whole-pixel frames, or RTW_TRACE_MIN);
  * -1 each before the first frame.  Synchronous; diagnostics only. */
 RTW_API int rtw_world_last_frame(rtw_gpu_world* gw, int* launches, int* whole_pixel, int* trace_min);
+/* The primary rays' per-tile leaf lists (include/rtw_beam.h) of that frame: tiles
+ * with a non-empty list, tiles with an empty list (their camera rays miss), tiles left to the SAH walk
+ * (list above the cap, degenerate beam), and the mean list length over the tiles that have one.  All 0
+ * when the frame used no lists (world out of scope, RTW_PRIMARY_LISTS=0, a kernel variant without them;
+ * then the kernel's name is "render_kernel<...>", with lists "render_kernel_pl<...>", same arguments). */
+RTW_API int rtw_world_last_frame_lists(rtw_gpu_world* gw, int* listed, int* empty, int* walked, double* mean_len);
+/* The lists the world holds, those of its last frame's shape: tile count (0: none), the cap and the builder
+ * kernel's time in ms; count[n_tiles] (entries, or -1: the tile takes the walk) and list[n_tiles * cap] are
+ * filled when not NULL.  Synchronous; tests and diagnostics. */
+RTW_API int rtw_world_primary_lists(rtw_gpu_world* gw, int32_t* n_tiles, int32_t* cap, double* build_ms,
+                                    int32_t* count, int32_t* list);
+/* The same lists built on the host by the same arithmetic (needs no GPU): params' width, height and tile
+ * shape; count[tiles], list[tiles * cap].  RTW_ERR_UNSUPPORTED unless every leaf is a plain cullable sphere. */
+RTW_API int rtw_primary_lists_host(const rtw_world* world, const rtw_render_params* params, int32_t cap,
+                                   int32_t* count, int32_t* list);
 /* Renders this partition's tiles into device buffer `d_out` (layout per params->layout) on
  * `stream` (a hipStream_t, NULL = default stream).  Asynchronous: returns after the launch. */
 RTW_API int rtw_render_device(rtw_gpu_world* gw, const rtw_render_params* params, float* d_out,

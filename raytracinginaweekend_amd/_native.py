@@ -268,6 +268,11 @@ _SIGS = {
     "rtw_world_kernel": (C.c_int, [_P] + [C.POINTER(C.c_int)] * 4),
     "rtw_world_kernel_name": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "rtw_world_last_frame": (C.c_int, [_P] + [C.POINTER(C.c_int)] * 3),
+    "rtw_world_last_frame_lists": (C.c_int, [_P] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_double)]),
+    "rtw_world_primary_lists": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rtw_primary_lists_host": (C.c_int, [C.POINTER(World), C.POINTER(RenderParams), C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]),
     "rtw_render_device": (C.c_int, [_P, C.POINTER(RenderParams), _P, _P]),
     "rtw_render_devices": (C.c_int, [C.POINTER(World), C.POINTER(RenderParams), C.POINTER(C.c_int), C.c_int,
                                      C.POINTER(C.c_float)]),

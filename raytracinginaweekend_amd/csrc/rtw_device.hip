@@ -34,6 +34,7 @@
 
 #include "../../include/rtw_scalar.h"
 #include "../../include/rtw_cull.h"
+#include "../../include/rtw_beam.h"
 #include "rtw_common.h"
 
 #ifndef RTW_BLOCK
@@ -75,6 +76,14 @@
 #define RTW_BATCH_SPREAD 8  // a batch is at most 1/(SPREAD x waves) of the launch's remaining items
 #endif
 #define RTW_STACK 32    // per-lane traversal stack (LDS), >= the BVH depth (checked at upload)
+// The primary rays' per-tile leaf lists (rtw_beam.h, render_kernel_pl): on by default (RTW_PRIMARY_LISTS=0 / 1
+// overrides), and the lanes that must hold a resolved ray before an iteration skips the walk
+#ifndef RTW_PL_DEFAULT
+#define RTW_PL_DEFAULT 1
+#endif
+#ifndef RTW_PL_SHADE_MIN
+#define RTW_PL_SHADE_MIN 16
+#endif
 #ifndef RTW_SAH_SPLIT_BUDGET
 #define RTW_SAH_SPLIT_BUDGET 1.0  // spatial splits in the SAH tree of triangle worlds: extra references per leaf
 #endif
@@ -258,6 +267,12 @@ struct KArgs {
     // the LDS triangle records' component stride (LDS mode 2: the triangle count)
     int32_t tri_prefix, tri_stride;
     int32_t tri_prefix_mat, tri_prefix_w;  // the prefix leaves' material and leaf_info.w (ShadeTabsT PRE)
+    // the primary rays' per-tile leaf lists (rtw_beam.h; render_kernel_pl only): per global tile the number of
+    // listed leaves (RTW_BEAM_WALK: the tile's camera rays take the walk) and pl_cap leaf indices; pl_shade_min:
+    // with at least that many lanes waiting for shading an iteration skips the walk
+    const int32_t* pl_count;
+    const int32_t* pl_list;
+    int32_t pl_cap, pl_shade_min;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -2183,8 +2198,22 @@ __device__ __forceinline__ int mb_take(uint32_t* mb, int v0, int& j) {
     }
 }
 
-template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP>
+// the walk's take() for a root found outside it (the primary rays' leaf lists, render_body's PL): te stays
+// succ(closest t), a second leaf reporting exactly the closest t flags a tie
+__device__ __forceinline__ void sah_take(Trav& T, float t, int leaf) {
+    const bool same = T.found >= 0 && t == __int_as_float(__float_as_int(T.te) - 1);
+    const bool tie = same && T.found != leaf;
+    T.fast = same ? (tie ? (T.fast | RTW_TF_TIE) : T.fast) : (T.fast & ~RTW_TF_TIE);
+    T.te = same ? T.te : __int_as_float(__float_as_int(t) + 1);
+    T.found = same ? T.found : leaf;
+}
+
+// PL (render_kernel_pl): camera rays of tiles that have a leaf list (rtw_beam.h) find their closest hit by
+// testing the listed leaves instead of walking the SAH tree.  Plain-sphere SAH worlds in LDS mode 1 only; every
+// other variant compiles none of it.
+template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool PL = false>
 __device__ __forceinline__ void render_body(const KArgs& A) {
+    static_assert(!PL || (LDS == 1 && LK == LK_SPHERES && !GEN), "leaf lists: plain-sphere worlds, LDS mode 1");
     constexpr bool LDS_SCENE = LDS >= 1;
     // LDS: [scene: nodes (2 float4 each), leaf records (1 float4 each), cull constants (1 float2
     // per node)] [stack: depth x BLOCK]
@@ -2280,6 +2309,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
     T.te = F32_INF;
     T.found = -1;
     bool fresh = false;  // T.ray is new: the traversal state must be initialised
+    bool cam = false;    // (PL) ... and it is a camera ray
     uint64_t c_mark = STATS ? clock64() : 0;  // execution-time split (counting variant only)
 
     // rendering.rs:174-176: jitter (x then y), then Camera::ray
@@ -2295,6 +2325,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
         acc = v3(0.0f, 0.0f, 0.0f);
         depth = A.max_depth;
         fresh = true;
+        if (PL) cam = true;
         RTW_PT(back);
     };
 
@@ -2519,6 +2550,27 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
             T.te = F32_INF;
             T.found = -1;
             if (STATS) st.c[ST_RAYS]++;
+            if constexpr (PL) {
+                // a camera ray of a listed tile: the tile's leaves through the walk's own sphere test and take(),
+                // te = inf at the start; it leaves as the walk would (PH_SHADE, RTW_TF_SAH, te = succ(t), the tie
+                // flag), an empty list as a miss.  The tile from the slot (slot = local tile x tile pixels + pixel):
+                // no register is kept for it.  Lanes of one wave almost always share the tile, but need not.
+                if (cam && rp.fast && sah) {
+                    const uint32_t tile = (uint32_t)A.part_index + fdiv(slot, A.fd_tile) * (uint32_t)A.part_count;
+                    const int32_t n = A.pl_count[tile];
+                    if (n >= 0) {
+                        const int32_t* __restrict__ L = A.pl_list + (size_t)tile * (uint32_t)A.pl_cap;
+                        const float4* fast = smem + A.fast_off;
+                        for (int32_t j = 0; j < n; ++j) {
+                            const int32_t leaf = L[j];
+                            float t;
+                            if (STATS) st.c[ST_T_SPHERE]++;  // a list test is a sphere test; the lists cost no node visits
+                            if (sphere_t(fast[leaf], T.ray, 0.001f, T.te, t)) sah_take(T, t, leaf);
+                        }
+                        T.phase = PH_SHADE;
+                    }
+                }
+            }
         }
 
         // 3. traversal (hittable.rs:429-473)
@@ -2532,7 +2584,12 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
 #ifdef RTW_WAVE_TIMING
             uint64_t wx_t0 = wall_clock64();
 #endif
-            T = traverse<STATS, LDS, LK, true, TM_SAH>(A.wdev, stabs, T, __builtin_amdgcn_readfirstlane(trace_min), A.node_count,
+            // (PL) with at least pl_shade_min lanes holding a resolved ray the iteration skips the walk: a
+            // threshold above the wave size makes the loop leave at its first exit check (some lane waits), so
+            // the lanes go straight to the proof and the one shade call; with fewer they wait through one round
+            int32_t tmin = __builtin_amdgcn_readfirstlane(trace_min);
+            if (PL && (int32_t)__popcll(__ballot(T.phase == PH_SHADE)) >= A.pl_shade_min) tmin = 65;
+            T = traverse<STATS, LDS, LK, true, TM_SAH>(A.wdev, stabs, T, tmin, A.node_count,
                                                        A.leaf_count, A.rect_count, A.tri_prefix, A.tri_stride, stack_off,
                                                        STATS ? A.stats + ST_COUNT : nullptr, dry_coop ? A.coop_max : -1);
             // the rays coop_solve takes (one call site, inlined: as an out-of-line call taking and
@@ -2767,6 +2824,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                 }
             } else {
                 fresh = true;  // the scattered ray continues the path
+                if (PL) cam = false;
             }
         }
     }
@@ -2848,6 +2906,44 @@ __global__ __launch_bounds__(RTW_BLOCK, RTW_MIN_WAVES_PER_SIMD) void render_kern
     }
 #endif
 }
+// The same kernel with the primary rays' leaf lists (render_body's PL), under a name of its own with the same
+// six arguments: the other variants keep their names and their code.
+template <bool STATS, int LDS, int LK, int TX, bool GEN = false, bool WP = false>
+__global__ __launch_bounds__(RTW_BLOCK, RTW_MIN_WAVES_PER_SIMD) void render_kernel_pl(KArgs A) {
+    render_body<STATS, LDS, LK, TX, GEN, WP, true>(A);
+}
+
+// The list builder: one tile per 64-thread group, every leaf tested by rtw_beam.h's rule (the host builder's
+// arithmetic, rtw_beam_tile_list), entries in leaf order.  Runs once per (world, frame size, tile shape, cap).
+#define RTW_PL_GROUP 64
+__global__ __launch_bounds__(RTW_PL_GROUP) void primary_lists_kernel(const rtw_camera* __restrict__ cam,
+                                                                      const float4* __restrict__ fast, int32_t leaf_count,
+                                                                      int32_t W, int32_t H, int32_t tw, int32_t th,
+                                                                      int32_t tiles_x, int32_t n_tiles, int32_t cap,
+                                                                      int32_t* __restrict__ count, int32_t* __restrict__ list) {
+    const int32_t tile = (int32_t)blockIdx.x;
+    if (tile >= n_tiles) return;  // (block-uniform)
+    const int lane = threadIdx.x;
+    rtw_beam_tile t;
+    rtw_beam_tile_setup(cam, W, H, tw, th, tile % tiles_x, tile / tiles_x, &t);
+    int32_t n = 0;
+    bool walk = !t.ok;
+    for (int32_t base = 0; base < leaf_count && !walk; base += RTW_PL_GROUP) {  // (block-uniform loop)
+        const int32_t i = base + lane;
+        bool in = false;
+        if (i < leaf_count) {
+            const float4 s = fast[i];
+            in = rtw_beam_sphere_in(&t, s.x, s.y, s.z, s.w) != 0;
+        }
+        const unsigned long long m = __ballot(in);
+        const int32_t at = n + (int32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (in && at < cap) list[(size_t)tile * (size_t)cap + at] = i;
+        n += (int32_t)__popcll(m);
+        if (n > cap) walk = true;
+    }
+    if (lane == 0) count[tile] = walk ? RTW_BEAM_WALK : n;
+}
+
 // Per slot: sum += colour of each sample of this launch, in sample order (the running sum of
 // earlier launches is carried in `running`); the last launch writes sum / spp (rendering.rs:179;
 // merge_planes with one plane multiplies by 1.0).
@@ -3712,6 +3808,18 @@ struct rtw_gpu_world {
     int32_t last_kernel[6] = {-1, -1, -1, -1, -1, -1};
     // the last frame: render launches, whole-pixel items, the default threshold, in-frame tuning on
     int32_t last_frame[4] = {-1, -1, -1, 0};
+    // the primary rays' per-tile leaf lists (rtw_beam.h, ensure_primary_lists): built on the device on the first
+    // frame of a (width, height, tile shape, cap), kept next to the cost order, indexed by global tile
+    bool pl_scope = false;         // the world's leaves are plain cullable spheres under the folded SAH tree
+    int32_t* pl_buf = nullptr;     // n_tiles counts, then n_tiles x cap leaf indices
+    int32_t pl_key[5] = {0, 0, 0, 0, 0};  // width, height, tile_w, tile_h, cap of pl_buf
+    int32_t pl_tiles = 0;
+    int32_t pl_info[3] = {0, 0, 0};  // tiles with a non-empty list, with an empty list, left to the walk
+    double pl_mean = 0.0;            // mean entries over the tiles that have a list
+    double pl_build_ms = 0.0;        // the builder kernel's time (device events)
+    int32_t last_pl = 0;             // the last render took render_kernel_pl
+    int32_t last_lists[3] = {0, 0, 0};  // pl_info of the last frame (zeros: the frame used no lists)
+    double last_mean = 0.0;
     uint64_t fingerprint = 0;  // rtw_world_fingerprint of the uploaded world (accumulator checkpoints)
     std::vector<struct rtw_accum*> accums;  // live accumulators: rtw_world_release orphans them (accum_orphan)
 };
@@ -4046,6 +4154,13 @@ extern "C" RTW_API int rtw_world_upload(const rtw_world* w, int device, rtw_gpu_
     // a plain-sphere world beyond the folded records' 2^14 nodes / leaves keeps an unfolded SAH tree: the
     // triangle loop (which tests plain spheres too) walks it with the one-child walk
     if (g->leaf_kinds == LK_SPHERES && g->sah_nodes > 0 && !g->sah_folded) g->leaf_kinds = LK_TRIS;
+    // the primary rays' leaf lists (rtw_beam.h): worlds of plain cullable spheres with the folded SAH tree
+    g->pl_scope = g->leaf_kinds == LK_SPHERES && g->sah_nodes > 0 && g->sah_folded;
+    for (int i = 0; i < w->leaf_count && g->pl_scope; ++i) {
+        const float c[3] = {lf[i].x, lf[i].y, lf[i].z};
+        float k, m, lo[3], hi[3];
+        if (!rtw_cull_sphere(c, lf[i].w, &k, &m, lo, hi)) g->pl_scope = false;
+    }
     for (int i = 0; i < w->node_count; ++i)
         for (int k = 0; k < 3; ++k)
             for (float c : {w->nodes[i].min[k], w->nodes[i].max[k]})
@@ -4203,7 +4318,7 @@ extern "C" RTW_API int rtw_world_kernel_name(rtw_gpu_world* g, char* buf, int ca
     if (!g || !buf || cap < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     char s[64] = "";
     if (g->last_kernel[0] >= 0)  // the product kernel: render_kernel<STATS = false, LDS, LK, TX, GEN, WP>
-        std::snprintf(s, sizeof(s), "render_kernel<false, %d, %d, %d, %s, %s>", g->last_kernel[0], g->last_kernel[1],
+        std::snprintf(s, sizeof(s), "render_kernel%s<false, %d, %d, %d, %s, %s>", g->last_pl ? "_pl" : "", g->last_kernel[0], g->last_kernel[1],
                       g->last_kernel[2], g->last_kernel[4] ? "true" : "false", g->last_kernel[5] ? "true" : "false");
     if ((int)std::strlen(s) >= cap) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "buffer too small");
     std::memcpy(buf, s, std::strlen(s) + 1);
@@ -4224,6 +4339,56 @@ extern "C" RTW_API int rtw_world_last_frame(rtw_gpu_world* g, int* launches, int
     return RTW_OK;
 }
 
+extern "C" RTW_API int rtw_world_last_frame_lists(rtw_gpu_world* g, int* listed, int* empty, int* walked, double* mean_len) {
+    if (!g || !listed || !empty || !walked || !mean_len) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    *listed = g->last_lists[0];
+    *empty = g->last_lists[1];
+    *walked = g->last_lists[2];
+    *mean_len = g->last_mean;
+    return RTW_OK;
+}
+
+// The lists the world holds (those of its last frame's shape): *n_tiles, *cap and the builder kernel's time;
+// count (n_tiles entries) and list (n_tiles x cap) are filled when not null.  No lists: *n_tiles = 0.
+extern "C" RTW_API int rtw_world_primary_lists(rtw_gpu_world* g, int32_t* n_tiles, int32_t* cap, double* build_ms,
+                                               int32_t* count, int32_t* list) {
+    if (!g || !n_tiles || !cap || !build_ms) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    *n_tiles = g->pl_buf ? g->pl_tiles : 0;
+    *cap = g->pl_buf ? g->pl_key[4] : 0;
+    *build_ms = g->pl_build_ms;
+    if (!g->pl_buf) return RTW_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    const size_t n = (size_t)g->pl_tiles;
+    if (count) HIP_TRY(hipMemcpy(count, g->pl_buf, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (list) HIP_TRY(hipMemcpy(list, g->pl_buf + n, n * (size_t)*cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RTW_OK;
+}
+
+// The same lists built on the host (rtw_beam_tile_list; needs no GPU): count[n_tiles], list[n_tiles x cap] for
+// params' width, height and tile shape.  RTW_ERR_UNSUPPORTED for a world with a leaf that is not a plain
+// cullable sphere.
+extern "C" RTW_API int rtw_primary_lists_host(const rtw_world* w, const rtw_render_params* p, int32_t cap, int32_t* count,
+                                              int32_t* list) {
+    if (!w || !p || !count || !list || cap < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument or cap < 1");
+    if (p->width < 2 || p->height < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "image width and height must be >= 2");
+    std::vector<float> fast((size_t)4 * std::max(0, w->leaf_count));
+    for (int32_t i = 0; i < w->leaf_count; ++i) {
+        const rtw_leaf& l = w->leaves[i];
+        float k, m, lo[3], hi[3];
+        if (l.flags != 0 || l.geom_kind != RTW_GEOM_SPHERE || l.geom_index < 0 || l.geom_index >= w->sphere_count ||
+            !rtw_cull_sphere(w->spheres[l.geom_index].center, w->spheres[l.geom_index].radius, &k, &m, lo, hi))
+            return rtw::fail(RTW_ERR_UNSUPPORTED, "leaf lists: plain cullable spheres only");
+        for (int c = 0; c < 3; ++c) fast[4 * (size_t)i + c] = w->spheres[l.geom_index].center[c];
+        fast[4 * (size_t)i + 3] = w->spheres[l.geom_index].radius;
+    }
+    const int32_t tw = p->tile_width > 0 ? p->tile_width : 8, th = p->tile_height > 0 ? p->tile_height : 8;
+    const int32_t tiles_x = (p->width + tw - 1) / tw, tiles_y = (p->height + th - 1) / th;
+    for (int32_t t = 0; t < tiles_x * tiles_y; ++t)
+        count[t] = rtw_beam_tile_list(&w->camera, p->width, p->height, tw, th, t % tiles_x, t / tiles_x, fast.data(),
+                                      w->leaf_count, cap, list + (size_t)t * cap);
+    return RTW_OK;
+}
+
 static void accum_orphan(struct rtw_accum* a);
 
 extern "C" RTW_API int rtw_world_release(rtw_gpu_world* g) {
@@ -4238,6 +4403,7 @@ extern "C" RTW_API int rtw_world_release(rtw_gpu_world* g) {
     if (g->tile_buf) (void)hipFree(g->tile_buf);
     if (g->sort_tmp) (void)hipFree(g->sort_tmp);
     if (g->running) (void)hipFree(g->running);
+    if (g->pl_buf) (void)hipFree(g->pl_buf);
     if (g->done) (void)hipEventDestroy(g->done);
     delete g;
     return RTW_OK;
@@ -4459,10 +4625,19 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
         return rtw::fail(RTW_ERR_UNSUPPORTED, "GEN kernel with a texture table in LDS");
     if (gen && acc_wp) return RTW_ACC_NO_WP;
     const int wp = A.whole_pixel ? 1 : 0;  // (never in the counting variant, render_frame_body)
-    const KFn kf = stats ? (sah ? fns_stats_sah[lk][mode] : fns_stats[mode])
-                 : gen   ? fns_gen[tx][lk - LK_WRAPPED][mode - 1]
-                         : fns[wp][tx][lk][mode];
+    KFn kf = stats ? (sah ? fns_stats_sah[lk][mode] : fns_stats[mode])
+             : gen   ? fns_gen[tx][lk - LK_WRAPPED][mode - 1]
+                     : fns[wp][tx][lk][mode];
+    // the primary rays' leaf lists (render_frame_body offers them): the plain-sphere SAH walk in LDS mode 1
+    static const KFn fns_pl[2][2] = {
+        {render_kernel_pl<false, 1, LK_SPHERES, TX_SOLID, false, false>, render_kernel_pl<false, 1, LK_SPHERES, TX_ANY, false, false>},
+        {render_kernel_pl<false, 1, LK_SPHERES, TX_SOLID, false, true>, render_kernel_pl<false, 1, LK_SPHERES, TX_ANY, false, true>}};
+    // (the counting variant follows them when it counts the product kernel's own traversal, stats_tree 1)
+    const bool pl = (!stats || ktree) && !gen && A.pl_count != nullptr && sah && lk == LK_SPHERES && mode == 1;
+    if (pl) kf = stats ? render_kernel_pl<true, 1, LK_SPHERES, TX_ANY> : fns_pl[wp][tx];
+    else A.pl_count = nullptr;
     if (!stats) {
+        g->last_pl = pl ? 1 : 0;
         g->last_kernel[0] = mode;
         g->last_kernel[1] = lk;
         g->last_kernel[2] = tx;
@@ -4547,6 +4722,59 @@ int grow(void** buf, size_t* have, size_t need) {
     const hipError_t e = hipMalloc(buf, need);
     if (e != hipSuccess) return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
     *have = need;
+    return RTW_OK;
+}
+
+// The primary rays' per-tile leaf lists for this frame's (width, height, tile shape): built on the device on
+// the first frame of the shape, then kept with the world.  RTW_PRIMARY_LISTS=0 switches them off,
+// RTW_PRIMARY_LIST_CAP sets the longest list (default 16, at most the leaf count; a tile with more takes the
+// walk), RTW_PRIMARY_SHADE_MIN the lanes that must wait for shading before an iteration skips the walk.
+int ensure_primary_lists(rtw_gpu_world* g, KArgs& A, hipStream_t stream) {
+    A.pl_count = nullptr;
+    A.pl_list = nullptr;
+    A.pl_cap = 0;
+    A.pl_shade_min = (int32_t)std::min<size_t>(65, env_size("RTW_PRIMARY_SHADE_MIN", RTW_PL_SHADE_MIN));
+    const char* e = std::getenv("RTW_PRIMARY_LISTS");
+    if (!g->pl_scope || g->leaf_count < 1 || !(e ? e[0] == '1' : RTW_PL_DEFAULT != 0)) return RTW_OK;
+    const int32_t cap = (int32_t)std::min<size_t>((size_t)g->leaf_count, env_size("RTW_PRIMARY_LIST_CAP", RTW_BEAM_CAP_DEFAULT));
+    const int32_t key[5] = {A.width, A.height, A.tile_w, A.tile_h, cap};
+    if (!g->pl_buf || std::memcmp(key, g->pl_key, sizeof(key)) != 0) {
+        if (g->pl_buf) (void)hipFree(g->pl_buf);
+        g->pl_buf = nullptr;
+        const size_t n = (size_t)A.n_tiles;
+        HIP_TRY(hipMalloc(&g->pl_buf, n * (size_t)(1 + cap) * sizeof(int32_t)));
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        HIP_TRY(hipEventCreate(&t0));
+        HIP_TRY(hipEventCreate(&t1));
+        HIP_TRY(hipEventRecord(t0, stream));
+        hipLaunchKernelGGL(primary_lists_kernel, dim3((unsigned)n), dim3(RTW_PL_GROUP), 0, stream, &g->w.wc->cam, g->w.leaf_fast,
+                           g->leaf_count, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.n_tiles, cap, g->pl_buf,
+                           g->pl_buf + n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(t1, stream));
+        std::vector<int32_t> cnt(n);
+        HIP_TRY(hipMemcpyAsync(cnt.data(), g->pl_buf, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        (void)hipEventDestroy(t0);
+        (void)hipEventDestroy(t1);
+        g->pl_build_ms = ms;
+        int64_t sum = 0;
+        g->pl_info[0] = g->pl_info[1] = g->pl_info[2] = 0;
+        for (int32_t c : cnt) {
+            ++g->pl_info[c < 0 ? 2 : c == 0 ? 1 : 0];
+            if (c > 0) sum += c;
+        }
+        const int32_t with_list = g->pl_info[0] + g->pl_info[1];
+        g->pl_mean = with_list > 0 ? (double)sum / with_list : 0.0;
+        g->pl_tiles = A.n_tiles;
+        std::memcpy(g->pl_key, key, sizeof(key));
+    }
+    if (g->pl_info[0] + g->pl_info[1] == 0) return RTW_OK;  // every tile walks: the parent's kernel
+    A.pl_count = g->pl_buf;
+    A.pl_list = g->pl_buf + (size_t)g->pl_tiles;
+    A.pl_cap = cap;
     return RTW_OK;
 }
 
@@ -4696,6 +4924,10 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         A.slot_cost = g->slot_cost;
         if (g->order_valid) A.tile_perm = g->tile_buf + 3 * (size_t)n_tiles_local;
     }
+    if (!stats || A.stats_tree == 1) {  // (tree = 0 counts the reference's traversal)
+        rc = ensure_primary_lists(g, A, stream);
+        if (rc != RTW_OK) return rc;
+    }
     HIP_TRY(hipMemsetAsync(g->queue, 0, RTW_QUEUE_BYTES, stream));
     int launch = 0;
     for (uint32_t s0 = 0; s0 < A.spp; s0 += (uint32_t)per_launch, ++launch) {
@@ -4747,6 +4979,8 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         g->last_frame[1] = A.whole_pixel ? 1 : 0;
         g->last_frame[2] = A.trace_min;
         g->last_frame[3] = A.tune ? 1 : 0;
+        for (int i = 0; i < 3; ++i) g->last_lists[i] = g->last_pl ? g->pl_info[i] : 0;
+        g->last_mean = g->last_pl ? g->pl_mean : 0.0;
     }
     if (A.slot_cost && n_tiles_local > 0) {  // the next frame's tile order
         uint32_t* tb = g->tile_buf;

@@ -189,10 +189,12 @@ class DeviceWorld:
         check(lib().rtw_world_kernel(self._h, C.byref(m), C.byref(lk), C.byref(tx), C.byref(tr)))
         name = C.create_string_buffer(64)
         check(lib().rtw_world_kernel_name(self._h, name, 64))
-        return {"lds_mode": m.value, "leaf_kinds": lk.value, "tex_kinds": tx.value,
-                "tree": ("reference", "sah")[tr.value] if tr.value >= 0 else None,
-                # the exact template name (GEN included), as rocprofv3's Kernel_Name holds it
-                "name": name.value.decode()}
+        out = {"lds_mode": m.value, "leaf_kinds": lk.value, "tex_kinds": tx.value,
+               "tree": ("reference", "sah")[tr.value] if tr.value >= 0 else None,
+               # the exact template name (GEN included), as rocprofv3's Kernel_Name holds it
+               "name": name.value.decode()}
+        out.update(self._lists())  # the primary rays' leaf lists of the last frame
+        return out
 
     def last_frame(self) -> dict:
         """The shape of the last frame: render launches, whole-pixel work items (no colour buffer),
@@ -202,7 +204,35 @@ class DeviceWorld:
             return {"launches": None, "whole_pixel": None, "trace_min": self.tuned_trace_min()}
         n, wp, tm = C.c_int(), C.c_int(), C.c_int()
         check(lib().rtw_world_last_frame(self._h, C.byref(n), C.byref(wp), C.byref(tm)))
-        return {"launches": n.value, "whole_pixel": bool(wp.value == 1), "trace_min": tm.value}
+        out = {"launches": n.value, "whole_pixel": bool(wp.value == 1), "trace_min": tm.value}
+        out.update(self._lists())
+        return out
+
+    def _lists(self) -> dict:
+        """The primary rays' per-tile leaf lists of the last frame (rtw_world_last_frame_lists): tiles with a
+        list, with an empty list, left to the walk, and the mean list length; zeros when the frame used none."""
+        if not hasattr(lib(), "rtw_world_last_frame_lists"):  # an older experiment build (A/B runs)
+            return {}
+        a, b, c, m = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        check(lib().rtw_world_last_frame_lists(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(m)))
+        return {"tiles_listed": a.value, "tiles_empty": b.value, "tiles_walked": c.value,
+                "mean_list_length": round(m.value, 3)}
+
+    def primary_lists(self):
+        """(count[tiles], list[tiles, cap], builder kernel ms) of the lists the world holds (those of its last
+        frame's shape), or None when it holds none.  count -1: the tile's camera rays take the walk."""
+        import numpy as np
+
+        n, cap, ms = C.c_int32(), C.c_int32(), C.c_double()
+        check(lib().rtw_world_primary_lists(self._h, C.byref(n), C.byref(cap), C.byref(ms), None, None))
+        if n.value == 0:
+            return None
+        count = np.zeros(n.value, np.int32)
+        lst = np.zeros((n.value, cap.value), np.int32)
+        i32p = C.POINTER(C.c_int32)
+        check(lib().rtw_world_primary_lists(self._h, C.byref(n), C.byref(cap), C.byref(ms), count.ctypes.data_as(i32p),
+                                            lst.ctypes.data_as(i32p)))
+        return count, lst, ms.value
 
     def collect_stats(self, params: N.RenderParams, tree: int = 0) -> dict:
         """Traversal statistics of one counting-variant render: tree 0 the reference's traversal
