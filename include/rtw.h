@@ -344,9 +344,22 @@ RTW_API int rtw_render_device(rtw_gpu_world* gw, const rtw_render_params* params
  * on worlds whose kernel keeps the generic leaf tables in LDS (wrapped, box or volume leaves: the
  * "true" in the fifth place of rtw_world_kernel_name), which add single samples.  One with
  * RTW_ACCUM_MOMENTS always takes single-sample items, its squares being summed in the accumulate
- * pass.  rtw_world_last_frame reports an add like a frame.  DESIGN.md 5.5c. */
+ * pass.  rtw_world_last_frame reports an add like a frame.  DESIGN.md 5.5c.
+ *
+ * Adaptive sampling (RTW_ACCUM_ADAPTIVE, needs RTW_ACCUM_MOMENTS).  The accumulator also
+ * keeps one uint32_t tile_stop per local tile (the partition's tiles in slot order): 0 = the tile is
+ * active, any other value = the sample count at which it stopped.  A stopped tile stays stopped, so every
+ * active tile holds exactly info.samples samples and a tile's count is
+ *   tile_stop[t] ? tile_stop[t] : info.samples.
+ * rtw_accum_adapt stops converged tiles, rtw_accum_add renders the active tiles only, and the resolves
+ * divide by the tile's own count.  The contract moves from the frame to the tile: a tile that stopped at
+ * n holds, bit for bit, the pixels of a frame at samples_per_pixel = n (and of the reference at that
+ * spp); the stop decision is a fixed f32 expression of the sums and squares (include/rtw_adapt.h), so a
+ * host can replay the whole run; the stop map is part of the output.  Like every accumulator with
+ * moments, an adaptive one takes single-sample work items. */
 typedef struct rtw_accum rtw_accum;
-#define RTW_ACCUM_MOMENTS 1u /* also keep per-channel sums of squares (the noise estimate) */
+#define RTW_ACCUM_MOMENTS 1u  /* also keep per-channel sums of squares (the noise estimate) */
+#define RTW_ACCUM_ADAPTIVE 2u /* per-tile stop map: converged tiles take no more samples */
 typedef struct rtw_accum_info { /* all fields fixed-width, no padding; also the checkpoint header */
     uint32_t version; /* 1 */
     uint32_t flags;   /* RTW_ACCUM_* */
@@ -370,11 +383,17 @@ RTW_API int rtw_accum_release(rtw_accum* a);
  * in sample order (with RTW_ACCUM_MOMENTS also sq = sq + c * c per channel, product and sum each
  * rounded to f32).  Asynchronous on `stream`; one add may be several launches (colour-buffer
  * budget, RTW_CHUNK).  n == 0 does nothing; samples + n beyond 32 bits is
- * RTW_ERR_INVALID_ARGUMENT. */
+ * RTW_ERR_INVALID_ARGUMENT.  An adaptive accumulator renders samples [samples, samples + n) of its
+ * active tiles only (the sums, squares and colours of stopped tiles are not touched) and advances
+ * info.samples only when at least one tile is active; with no active tile the call does nothing and
+ * returns RTW_OK.  While every tile is active it runs exactly the launches of a plain moments
+ * accumulator; with fewer, the launch walks the active tiles in the world's learned cost order
+ * (costliest first; tile order before one is learned), each tile's samples together. */
 RTW_API int rtw_accum_add(rtw_accum* a, uint32_t n_samples, void* stream);
 RTW_API int rtw_accum_get_info(rtw_accum* a, rtw_accum_info* out); /* host bookkeeping, no sync */
 /* sum / (float)samples into device buffer d_out, in params->layout.  Non-destructive; needs
- * samples >= 1.  Asynchronous. */
+ * samples >= 1.  Asynchronous.
+ * (Adaptive: here and in the standard error and the noise estimate, `samples` is the tile's own count.) */
 RTW_API int rtw_accum_resolve(rtw_accum* a, float* d_out, void* stream);
 /* The standard error of the mean per channel (needs RTW_ACCUM_MOMENTS and samples >= 2), in f32:
  * nf = (float)samples; mean = sum / nf; d = sq - sum * mean; var = (d < 0 ? 0 : d) / (float)(samples - 1);
@@ -385,6 +404,24 @@ RTW_API int rtw_accum_resolve_stderr(rtw_accum* a, float* d_out, void* stream);
  * not finite; *pixels_counted = pixels that entered the mean (0: *noise = 0).  Same conditions as the
  * stderr.  Synchronous. */
 RTW_API int rtw_accum_noise(rtw_accum* a, void* stream, double* noise, int64_t* pixels_counted);
+/* The samples each pixel holds (the tile's count), one uint32_t per pixel (RTW_LAYOUT_IMAGE; pixels of other
+ * partitions are left alone) or per slot (RTW_LAYOUT_TILES; padding slots get 0).  Any accumulator: without
+ * RTW_ACCUM_ADAPTIVE every count is info.samples.  Asynchronous. */
+RTW_API int rtw_accum_resolve_samples(rtw_accum* a, uint32_t* d_out, void* stream);
+/* RTW_ACCUM_ADAPTIVE only (else RTW_ERR_INVALID_ARGUMENT), samples >= 2 and min_samples >= 2.  For every active
+ * tile: E = the maximum over the tile's owned pixels of the f32 value e of rtw_accum_noise, leaving out pixels
+ * whose e is not finite (no finite pixel: E = 0); if samples >= min_samples and E <= target then
+ * tile_stop[t] = samples.  Returns the tiles and the owned pixels that are still active.  The arithmetic is
+ * include/rtw_adapt.h's; rtw_adapt_tiles_host runs it on host arrays.  Synchronous. */
+RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_samples, void* stream, int64_t* active_tiles,
+                            int64_t* active_pixels);
+/* The same decision on exported state, without a GPU: sums and squares as rtw_accum_export gives them for
+ * params' geometry (width, height, tile shape, part), tile_stop[local tiles] updated in place. */
+RTW_API int rtw_adapt_tiles_host(const float* sums, const float* squares, const rtw_render_params* params,
+                                 uint32_t samples, float target, uint32_t min_samples, uint32_t* tile_stop);
+/* Copies the stop map (one entry per local tile = slots / (tile_width * tile_height)) to the host.
+ * RTW_ACCUM_ADAPTIVE only.  Synchronous. */
+RTW_API int rtw_accum_tile_stops(rtw_accum* a, uint32_t* host_stop);
 /* Copies the sums (and, with moments, the squares; host_squares may be NULL otherwise) to the host,
  * 3 * slots floats each, in slot order (tile-major); padding slots of edge tiles hold zeros.
  * Synchronous. */
@@ -394,6 +431,13 @@ RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares
  * slots, else RTW_ERR_INVALID_ARGUMENT with a message naming the field.  Synchronous. */
 RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                              const float* host_squares);
+/* The checkpoint of an adaptive accumulator: rtw_accum_export plus the stop map, and its import.  `info` is
+ * checked as in rtw_accum_import (its flags hold RTW_ACCUM_ADAPTIVE; rtw_accum_info stays version 1); a
+ * tile_stop entry of 1 or above info->samples is refused with a message naming tile_stop.  Plain
+ * rtw_accum_import on an adaptive accumulator is refused too (it has no tile_stop to set). */
+RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_tile_stop);
+RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                      const float* host_squares, const uint32_t* host_tile_stop);
 
 /* Floats needed by one partition's RTW_LAYOUT_TILES buffer (tiles * tile_w * tile_h * 3). */
 RTW_API int rtw_partition_floats(const rtw_render_params* params, int64_t* floats);

@@ -9,6 +9,7 @@ from . import image_io
 from .progressive import (
     Accumulator,
     AccumState,
+    render_adaptive,
     render_progressive,
     render_to_noise,
     world_fingerprint,
@@ -58,6 +59,7 @@ __all__ = [
     "load_obj_mesh",
     "render",
     "render_devices",
+    "render_adaptive",
     "render_params",
     "render_progressive",
     "render_to_noise",

@@ -191,6 +191,7 @@ class RenderStats(C.Structure):
 
 
 ACCUM_MOMENTS = 1  # RTW_ACCUM_MOMENTS
+ACCUM_ADAPTIVE = 2  # RTW_ACCUM_ADAPTIVE
 
 
 class AccumInfo(C.Structure):  # rtw_accum_info: fixed-width fields, no padding (also the checkpoint header)
@@ -290,6 +291,16 @@ _SIGS = {
     "rtw_accum_noise": (C.c_int, [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "rtw_accum_export": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "rtw_accum_import": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "rtw_accum_resolve_samples": (C.c_int, [_P, _P, _P]),
+    "rtw_accum_adapt": (C.c_int, [_P, C.c_float, C.c_uint32, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rtw_adapt_tiles_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(RenderParams), C.c_uint32,
+                                       C.c_float, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rtw_accum_tile_stops": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "rtw_accum_export_adaptive": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "rtw_accum_import_adaptive": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_uint32)]),
+    "rtw_debug_compact": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rtw_partition_floats": (C.c_int, [C.POINTER(RenderParams), C.POINTER(C.c_int64)]),
     "rtw_untile_device": (C.c_int, [C.POINTER(RenderParams), _P, C.c_int64, _P, _P]),
     "rtw_render_collect_stats": (C.c_int, [_P, C.POINTER(RenderParams), C.POINTER(RenderStats)]),

@@ -35,6 +35,7 @@
 #include "../../include/rtw_scalar.h"
 #include "../../include/rtw_cull.h"
 #include "../../include/rtw_beam.h"
+#include "../../include/rtw_adapt.h"
 #include "rtw_common.h"
 
 #ifndef RTW_BLOCK
@@ -2993,11 +2994,15 @@ __device__ __forceinline__ bool slot_pixel(const SlotGeom& G, uint32_t slot, int
 }
 // An accumulator's add with RTW_ACCUM_MOMENTS: accumulate_kernel's in-order sum onto the accumulator's
 // own running sum, and per channel sq = add(sq, mul(c, c)) (two roundings: no contraction in this build).
+// tile_stop (adaptive accumulators with a stopped tile, else null): the slots of stopped tiles are skipped --
+// the launch rendered the active tiles only, so their colour-buffer entries are stale.
 __global__ void accumulate_moments_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G,
-                                          float* __restrict__ sums, float* __restrict__ squares) {
+                                          float* __restrict__ sums, float* __restrict__ squares,
+                                          const uint32_t* __restrict__ tile_stop) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     int32_t px, py;
     if (!slot_pixel(G, slot, px, py)) return;
+    if (tile_stop && tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)] != 0) return;
     float* S = sums + 3 * (size_t)slot;
     float* Q = squares + 3 * (size_t)slot;
     V3 sum = v3(S[0], S[1], S[2]), sq = v3(Q[0], Q[1], Q[2]);
@@ -3014,28 +3019,45 @@ __global__ void accumulate_moments_kernel(const float* __restrict__ colors, uint
     Q[1] = sq.y;
     Q[2] = sq.z;
 }
-// the standard error of a channel's mean from its sum and sum of squares (rtw.h: the order is the contract)
+// the standard error of a channel's mean from its sum and sum of squares (rtw.h: the order is the contract;
+// the arithmetic is rtw_adapt.h's, shared with the host)
 __device__ __forceinline__ float accum_se(float sum, float sq, uint32_t samples, float& mean) {
-    const float nf = (float)samples;
-    mean = sum / nf;
-    const float d = sq - sum * mean;
-    const float var = (d < 0.0f ? 0.0f : d) / (float)(samples - 1);  // a NaN d stays NaN
-    return __builtin_sqrtf(var / nf);
+    return rtw_adapt_se(sum, sq, samples, &mean);
 }
-// what 0: sum / samples (accumulate_kernel's last step); 1: the standard error (needs squares)
+// the samples a slot holds: its tile's stop count, or the accumulator's frontier (tile_stop null: not adaptive)
+__device__ __forceinline__ uint32_t slot_samples(const SlotGeom& G, uint32_t slot, const uint32_t* tile_stop,
+                                                 uint32_t samples) {
+    if (!tile_stop) return samples;
+    const uint32_t stop = tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)];
+    return stop ? stop : samples;
+}
+// what 0: sum / samples (accumulate_kernel's last step); 1: the standard error (needs squares); 2: the sample
+// count itself, one uint32_t per pixel or slot (padding slots of a tile buffer: 0)
 __global__ void accum_resolve_kernel(const float* __restrict__ sums, const float* __restrict__ squares, SlotGeom G,
-                                     uint32_t samples, int what, float* out, int layout) {
+                                     uint32_t samples, const uint32_t* __restrict__ tile_stop, int what, float* out,
+                                     int layout) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     int32_t px, py;
-    if (!slot_pixel(G, slot, px, py)) return;
+    const bool owned = slot_pixel(G, slot, px, py);
+    if (what == 2) {
+        uint32_t* o = (uint32_t*)out;
+        if (layout == RTW_LAYOUT_TILES) {
+            if (slot < G.total) o[slot] = owned ? slot_samples(G, slot, tile_stop, samples) : 0u;
+        } else if (owned) {
+            o[(size_t)py * G.width + px] = slot_samples(G, slot, tile_stop, samples);
+        }
+        return;
+    }
+    if (!owned) return;
+    const uint32_t n = slot_samples(G, slot, tile_stop, samples);
     const float* S = sums + 3 * (size_t)slot;
     V3 r;
     if (what == 0) {
-        r = divs(v3(S[0], S[1], S[2]), (float)samples);
+        r = divs(v3(S[0], S[1], S[2]), (float)n);
     } else {
         const float* Q = squares + 3 * (size_t)slot;
         float m;
-        r = v3(accum_se(S[0], Q[0], samples, m), accum_se(S[1], Q[1], samples, m), accum_se(S[2], Q[2], samples, m));
+        r = v3(accum_se(S[0], Q[0], n, m), accum_se(S[1], Q[1], n, m), accum_se(S[2], Q[2], n, m));
     }
     float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
     o[0] = r.x;
@@ -3047,7 +3069,9 @@ __global__ void accum_resolve_kernel(const float* __restrict__ sums, const float
 #define RTW_NOISE_BLOCK 256
 __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const float* __restrict__ sums,
                                                                       const float* __restrict__ squares, SlotGeom G,
-                                                                      uint32_t samples, double* __restrict__ part_sum,
+                                                                      uint32_t samples,
+                                                                      const uint32_t* __restrict__ tile_stop,
+                                                                      double* __restrict__ part_sum,
                                                                       uint32_t* __restrict__ part_count) {
     __shared__ double sh_sum[RTW_NOISE_BLOCK];
     __shared__ uint32_t sh_cnt[RTW_NOISE_BLOCK];
@@ -3056,14 +3080,9 @@ __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const floa
     uint32_t n = 0;
     int32_t px, py;
     if (slot_pixel(G, slot, px, py)) {
-        const float* S = sums + 3 * (size_t)slot;
-        const float* Q = squares + 3 * (size_t)slot;
-        float mr, mg, mb;
-        const float sr = accum_se(S[0], Q[0], samples, mr);
-        const float sg = accum_se(S[1], Q[1], samples, mg);
-        const float sb = accum_se(S[2], Q[2], samples, mb);
-        const float e = ((sr + sg) + sb) / (((mr + mg) + mb) + 0.01f);
-        if (__builtin_fabsf(e) < F32_INF) {  // finite (false for NaN)
+        const float e = rtw_adapt_pixel(sums + 3 * (size_t)slot, squares + 3 * (size_t)slot,
+                                        slot_samples(G, slot, tile_stop, samples));
+        if (rtw_adapt_finite(e)) {  // (false for NaN)
             v = (double)e;
             n = 1;
         }
@@ -3082,6 +3101,80 @@ __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const floa
         part_sum[blockIdx.x] = sh_sum[0];
         part_count[blockIdx.x] = sh_cnt[0];
     }
+}
+
+// ---- adaptive sampling (RTW_ACCUM_ADAPTIVE) ------------------------------------------
+// rtw_accum_adapt's tile test: one wave per local tile (RTW_ADAPT_BLOCK / 64 tiles per block; nothing depends
+// on which block runs where).  The lanes stride over the tile's slots, each keeps the maximum of its pixels'
+// finite e (rtw_adapt.h), a 64-lane butterfly maximum follows, and lane 0 stores the tile's stop.  Stopped
+// tiles are left alone.
+#define RTW_ADAPT_BLOCK 256
+__global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_kernel(const float* __restrict__ sums,
+                                                                      const float* __restrict__ squares,
+                                                                      rtw_adapt_geom G, uint32_t samples, float target,
+                                                                      uint32_t min_samples,
+                                                                      uint32_t* __restrict__ tile_stop) {
+    const int32_t lane = (int32_t)(threadIdx.x & 63u);
+    const int64_t lt64 = (int64_t)blockIdx.x * (RTW_ADAPT_BLOCK / 64) + (int64_t)(threadIdx.x >> 6);
+    if (lt64 >= (int64_t)G.local_tiles) return;  // wave-uniform
+    const int32_t lt = (int32_t)lt64;
+    if (tile_stop[lt] != 0) return;  // wave-uniform: a stopped tile stays stopped
+    const int32_t per_tile = G.tile_w * G.tile_h;
+    float E = rtw_adapt_none();
+    for (int32_t it = lane; it < per_tile; it += 64) {
+        int32_t px, py;
+        if (!rtw_adapt_slot_pixel(&G, lt, it, &px, &py)) continue;
+        const size_t at = 3 * ((size_t)lt * (size_t)per_tile + (size_t)it);
+        E = rtw_adapt_max(E, rtw_adapt_pixel(sums + at, squares + at, samples));
+    }
+    for (int off = 32; off > 0; off >>= 1) {  // every lane's E is finite or -inf: the maximum has no order
+        const float o = __shfl_xor(E, off, 64);
+        E = o > E ? o : E;
+    }
+    if (lane == 0) {
+        const uint32_t stop = rtw_adapt_stop(rtw_adapt_tile_e(E), samples, target, min_samples);
+        if (stop) tile_stop[lt] = stop;
+    }
+}
+
+// The active tiles of `order` (null: 0, 1, 2, ...), in that order: a stable stream compaction by
+// tile_stop[t] == 0, so the learned cost order (costliest first) survives.  ONE block of RTW_COMPACT_BLOCK
+// threads walks the n entries in chunks of its size: per wave a 64-lane ballot and popcounts, the waves'
+// counts through LDS, the chunks' running total in a register every thread keeps alike.  out[0 .. K) gets
+// the tiles, *out_count = K.  An entry >= n (never in a sorted order; a debug caller's mistake) is dropped.
+#define RTW_COMPACT_BLOCK 1024
+__global__ __launch_bounds__(RTW_COMPACT_BLOCK) void compact_active_kernel(const uint32_t* __restrict__ order,
+                                                                           const uint32_t* __restrict__ tile_stop,
+                                                                           uint32_t n, uint32_t* __restrict__ out,
+                                                                           uint32_t* __restrict__ out_count) {
+    __shared__ uint32_t wave_count[RTW_COMPACT_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t done = 0;  // entries written by earlier chunks (block-uniform)
+    for (uint32_t base = 0; base < n; base += RTW_COMPACT_BLOCK) {  // (block-uniform trip count)
+        const uint32_t i = base + threadIdx.x;
+        uint32_t t = 0;
+        bool keep = false;
+        if (i < n) {
+            t = order ? order[i] : i;
+            keep = t < n && tile_stop[t] == 0;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_count[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < RTW_COMPACT_BLOCK / 64; ++w) {
+            const uint32_t c = wave_count[w];
+            before += w < wave ? c : 0u;
+            total += c;
+        }
+        if (keep) {
+            const unsigned long long below = lane == 0 ? 0ull : (m & (~0ull >> (64 - lane)));
+            out[done + before + (uint32_t)__popcll(below)] = t;  // < n: at most one entry per input
+        }
+        done += total;
+        __syncthreads();  // the next chunk overwrites wave_count
+    }
+    if (threadIdx.x == 0) *out_count = done;
 }
 
 // The reference's thread_count > 1 (rendering.rs:161-219): split_work_tasks gives plane t the
@@ -4675,8 +4768,9 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
 }
 
 // work items of one launch: chunks of `chunk` samples, then the last RTW_TAIL_SAMPLES (default 8)
-// samples of the launch's range one at a time
-void set_items(KArgs& A, uint32_t chunk);
+// samples of the launch's range one at a time.  active_tiles > 0: a launch over the first active_tiles
+// entries of A.tile_perm only (an adaptive accumulator's compacted order).
+void set_items(KArgs& A, uint32_t chunk, uint32_t active_tiles = 0);
 
 size_t env_size(const char* name, size_t dflt) {
     const char* e = std::getenv(name);
@@ -4691,14 +4785,16 @@ uint64_t queue_cap(uint64_t items) {
     return (gran + RTW_QUEUES - 1) / RTW_QUEUES * RTW_QGRAN;
 }
 
-void set_items(KArgs& A, uint32_t chunk) {
+void set_items(KArgs& A, uint32_t chunk, uint32_t active_tiles) {
     const uint32_t n = A.s_end - A.s_begin;
+    // the slots the launch walks: A.total and the colour buffer's stride stay the whole partition's
+    const uint64_t slots = active_tiles ? (uint64_t)active_tiles * (uint32_t)(A.tile_w * A.tile_h) : (uint64_t)A.total;
     // chunk-major order drains on single-sample items; in cost order the cheapest tiles come last
     const uint32_t tail = A.tile_perm || A.whole_pixel ? 0u : std::min<uint32_t>(n, (uint32_t)env_size("RTW_TAIL_SAMPLES", 8));
     A.chunk = chunk;
     A.s_split = A.s_end - tail;
-    A.items_big = (uint64_t)A.total * ((A.s_split - A.s_begin + chunk - 1) / chunk);
-    A.items = A.items_big + (uint64_t)A.total * tail;
+    A.items_big = slots * ((A.s_split - A.s_begin + chunk - 1) / chunk);
+    A.items = A.items_big + slots * tail;
     A.q_cap = queue_cap(A.items);
     A.chunks = (A.s_split - A.s_begin + chunk - 1) / chunk;
     // big batches after the first 10 % of the items: in cost order the costly tiles come first and a
@@ -4789,6 +4885,11 @@ struct AccumRun {
     float* sums;
     float* squares;  // null: no moments
     uint32_t base;   // samples the sums already hold
+    // adaptive accumulators with a stopped tile (else null / 0): the stop map, the buffer for the compacted
+    // tile order (local tiles + 1 entries: the list, then its length) and the active tiles K (host's count)
+    const uint32_t* tile_stop = nullptr;
+    uint32_t* active_perm = nullptr;
+    uint32_t active = 0;
 };
 int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStream_t stream,
                       std::vector<uint64_t>* launch_items, const AccumRun* acc, bool acc_allow_wp = true);
@@ -4924,6 +5025,16 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         A.slot_cost = g->slot_cost;
         if (g->order_valid) A.tile_perm = g->tile_buf + 3 * (size_t)n_tiles_local;
     }
+    // Fewer than all tiles active (adaptive accumulator): the launches walk the active tiles only, in the
+    // learned cost order when there is one, else in tile order -- RTW_NO_REORDER or a fresh key included:
+    // a subset is always a tile_perm launch.  The compaction is stable, so costliest-first survives.
+    const uint32_t active = acc && acc->tile_stop ? acc->active : 0u;
+    if (active) {
+        hipLaunchKernelGGL(compact_active_kernel, dim3(1), dim3(RTW_COMPACT_BLOCK), 0, stream, (const uint32_t*)A.tile_perm,
+                           acc->tile_stop, n_tiles_local, acc->active_perm, acc->active_perm + n_tiles_local);
+        HIP_TRY(hipGetLastError());
+        A.tile_perm = acc->active_perm;
+    }
     if (!stats || A.stats_tree == 1) {  // (tree = 0 counts the reference's traversal)
         rc = ensure_primary_lists(g, A, stream);
         if (rc != RTW_OK) return rc;
@@ -4935,7 +5046,7 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         // (an accumulator's samples continue where its sums stand: the RNG streams are keyed by sample)
         A.s_begin = (acc ? acc->base : 0u) + s0;
         A.s_end = (acc ? acc->base : 0u) + s1;
-        set_items(A, chunk);
+        set_items(A, chunk, active);
         A.queue = g->queue + (size_t)std::min(launch, RTW_QUEUE_SLOTS - 1) * RTW_QUEUE_BLOCK;
         if (launch_items) launch_items->push_back(A.items);
         if (acc && A.whole_pixel) {  // the lanes continue the accumulator's sums (KArgs::whole_pixel)
@@ -4955,7 +5066,7 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         } else if (acc && acc->squares) {
             const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
             hipLaunchKernelGGL(accumulate_moments_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
-                               s1 - s0, G, acc->sums, acc->squares);
+                               s1 - s0, G, acc->sums, acc->squares, acc->tile_stop);
         } else if (acc) {  // the one-shot frames' kernel as a middle launch: onto the sums, no division
             hipLaunchKernelGGL(accumulate_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors, s1 - s0,
                                A.total, acc->sums, 0, 0, A.spp, out, A.layout, A.width, A.height, A.tile_w, A.tile_h,
@@ -5029,6 +5140,12 @@ struct rtw_accum {
     float* squares = nullptr;  // the same with RTW_ACCUM_MOMENTS, else null
     double* noise_sum = nullptr;  // rtw_accum_noise: per-block partials (device), grown on first use
     uint32_t* noise_cnt = nullptr;
+    // RTW_ACCUM_ADAPTIVE: the stop map, the compacted tile order of the adds (tiles + 1
+    // entries), the host's copy of the map (kept current by adapt and import: the adds' K) and its zeros
+    uint32_t* tile_stop = nullptr;
+    uint32_t* active_perm = nullptr;
+    std::vector<uint32_t> h_stop;
+    uint32_t tiles = 0, active = 0;
 };
 
 // The world went first (rtw_world_release): the accumulator's device state goes with it, and every later
@@ -5038,6 +5155,9 @@ static void accum_orphan(rtw_accum* a) {
     if (a->squares) (void)hipFree(a->squares);
     if (a->noise_sum) (void)hipFree(a->noise_sum);
     if (a->noise_cnt) (void)hipFree(a->noise_cnt);
+    if (a->tile_stop) (void)hipFree(a->tile_stop);
+    if (a->active_perm) (void)hipFree(a->active_perm);
+    a->tile_stop = a->active_perm = nullptr;
     a->sums = a->squares = nullptr;
     a->noise_sum = nullptr;
     a->noise_cnt = nullptr;
@@ -5076,6 +5196,7 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
     if (what == 1 && !a->squares)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs an accumulator with RTW_ACCUM_MOMENTS");
     if (what == 1 && a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs samples >= 2");
+    // (what == 2, the sample counts: any accumulator at any point; a fresh one holds 0 everywhere)
     KArgs A;
     int rc = accum_args(a, 1, A);
     if (rc != RTW_OK) return rc;
@@ -5083,7 +5204,8 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
     rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
     hipLaunchKernelGGL(accum_resolve_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream, (const float*)a->sums,
-                       (const float*)a->squares, accum_geom(A), a->info.samples, what, d_out, A.layout);
+                       (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop, what, d_out,
+                       A.layout);
     HIP_TRY(hipGetLastError());
     return accum_leave(a, stream);
 }
@@ -5091,7 +5213,9 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
 
 extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t flags, rtw_accum** out) {
     if (!g || !p || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
-    if (flags & ~RTW_ACCUM_MOMENTS) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown accumulator flags");
+    if (flags & ~(RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown accumulator flags");
+    if ((flags & RTW_ACCUM_ADAPTIVE) && !(flags & RTW_ACCUM_MOMENTS))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "RTW_ACCUM_ADAPTIVE needs RTW_ACCUM_MOMENTS (the stop test reads the squares)");
     if (p->thread_count > 1)
         return rtw::fail(RTW_ERR_UNSUPPORTED,
                          "accumulators take thread_count 0 or 1: the reference's plane split depends on the final "
@@ -5127,6 +5251,13 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     const size_t bytes = std::max<size_t>(16, (size_t)A.total * 3 * sizeof(float));
     hipError_t e = hipMalloc(&a->sums, bytes);
     if (e == hipSuccess && (flags & RTW_ACCUM_MOMENTS)) e = hipMalloc(&a->squares, bytes);
+    a->tiles = a->active = A.total / (uint32_t)(A.tile_w * A.tile_h);
+    const size_t stop_bytes = ((size_t)a->tiles + 1) * sizeof(uint32_t);
+    if (flags & RTW_ACCUM_ADAPTIVE) {
+        a->h_stop.assign(a->tiles, 0u);
+        if (e == hipSuccess) e = hipMalloc(&a->tile_stop, stop_bytes);
+        if (e == hipSuccess) e = hipMalloc(&a->active_perm, stop_bytes);
+    }
     if (e != hipSuccess) {
         rtw_accum_release(a);
         return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -5134,6 +5265,8 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     // (synchronous: the zeros are there before any stream's first add)
     e = hipMemset(a->sums, 0, bytes);
     if (e == hipSuccess && a->squares) e = hipMemset(a->squares, 0, bytes);
+    if (e == hipSuccess && a->tile_stop) e = hipMemset(a->tile_stop, 0, stop_bytes);
+    if (e == hipSuccess && a->active_perm) e = hipMemset(a->active_perm, 0, stop_bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         rtw_accum_release(a);
@@ -5169,9 +5302,15 @@ extern "C" RTW_API int rtw_accum_add(rtw_accum* a, uint32_t n, void* stream) {
     KArgs A;
     const int v = accum_args(a, n, A);
     if (v != RTW_OK) return v;
+    if (a->tile_stop && a->active == 0) return RTW_OK;  // adaptive, every tile stopped: nothing to render
     A.out = nullptr;  // an add writes the accumulator's state only
     HIP_TRY(hipSetDevice(a->g->device));
-    const AccumRun run{a->sums, a->squares, a->info.samples};
+    AccumRun run{a->sums, a->squares, a->info.samples};
+    if (a->tile_stop && a->active < a->tiles) {  // (all active: exactly a plain moments accumulator's add)
+        run.tile_stop = a->tile_stop;
+        run.active_perm = a->active_perm;
+        run.active = a->active;
+    }
     const int rc = render_frame(a->g, A, false, nullptr, (hipStream_t)stream, nullptr, &run);
     if (rc != RTW_OK) return rc;
     a->info.samples += n;
@@ -5206,7 +5345,8 @@ extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* nois
         HIP_TRY(hipMalloc(&a->noise_cnt, (size_t)blocks * sizeof(uint32_t)));
     }
     hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, (const float*)a->sums,
-                       (const float*)a->squares, accum_geom(A), a->info.samples, a->noise_sum, a->noise_cnt);
+                       (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop, a->noise_sum,
+                       a->noise_cnt);
     HIP_TRY(hipGetLastError());
     rc = accum_leave(a, stream);
     if (rc != RTW_OK) return rc;
@@ -5226,7 +5366,8 @@ extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* nois
     return RTW_OK;
 }
 
-extern "C" RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares) {
+namespace {
+int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop) {
     if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
@@ -5236,11 +5377,12 @@ extern "C" RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* h
     if (bytes == 0) return RTW_OK;
     HIP_TRY(hipMemcpy(host_sums, a->sums, bytes, hipMemcpyDeviceToHost));
     if (a->squares) HIP_TRY(hipMemcpy(host_squares, a->squares, bytes, hipMemcpyDeviceToHost));
+    if (host_stop) HIP_TRY(hipMemcpy(host_stop, a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RTW_OK;
 }
 
-extern "C" RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
-                                        const float* host_squares) {
+int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums, const float* host_squares,
+                 const uint32_t* host_stop) {
     if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     const rtw_accum_info& M = a->info;
@@ -5261,14 +5403,147 @@ extern "C" RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info
     if (info->world_fingerprint != M.world_fingerprint) return differs("world_fingerprint");
     if (info->slots != M.slots) return differs("slots");
     if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
+    if (a->tile_stop && !host_stop)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT,
+                         "an adaptive accumulator's state includes tile_stop: import it with rtw_accum_import_adaptive");
+    if (!a->tile_stop && host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "tile_stop given, but the accumulator is not adaptive");
+    uint32_t active = a->tiles;
+    if (host_stop) {
+        active = 0;
+        for (uint32_t t = 0; t < a->tiles; ++t) {
+            if (host_stop[t] == 1 || host_stop[t] > info->samples)
+                return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "tile_stop[" + std::to_string(t) + "] = " + std::to_string(host_stop[t]) +
+                                                               ": a stop is 0 or within 2 .. samples (" +
+                                                               std::to_string(info->samples) + ")");
+            active += host_stop[t] == 0 ? 1u : 0u;
+        }
+    }
     HIP_TRY(hipSetDevice(a->g->device));
     if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
     const size_t bytes = (size_t)M.slots * 3 * sizeof(float);
     if (bytes > 0) {
         HIP_TRY(hipMemcpy(a->sums, host_sums, bytes, hipMemcpyHostToDevice));
         if (a->squares) HIP_TRY(hipMemcpy(a->squares, host_squares, bytes, hipMemcpyHostToDevice));
+        if (host_stop) HIP_TRY(hipMemcpy(a->tile_stop, host_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
+    if (host_stop) a->h_stop.assign(host_stop, host_stop + a->tiles);
+    a->active = active;
     a->info.samples = info->samples;
+    return RTW_OK;
+}
+
+// the owned pixels of local tile lt (edge tiles are cut by the frame)
+int64_t tile_pixels(const rtw_accum_info& I, uint32_t lt) {
+    const int32_t tiles_x = (I.width + I.tile_width - 1) / I.tile_width;
+    const int64_t tile = (int64_t)I.part_index + (int64_t)lt * I.part_count;
+    const int32_t x0 = (int32_t)(tile % tiles_x) * I.tile_width, y0 = (int32_t)(tile / tiles_x) * I.tile_height;
+    const int32_t w = std::max(0, std::min(I.tile_width, I.width - x0)), h = std::max(0, std::min(I.tile_height, I.height - y0));
+    return (int64_t)w * h;
+}
+}  // namespace
+
+extern "C" RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares) {
+    return accum_export(a, host_sums, host_squares, nullptr);
+}
+
+extern "C" RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                        const float* host_squares) {
+    return accum_import(a, info, host_sums, host_squares, nullptr);
+}
+
+extern "C" RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop) {
+    if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (a->g && !a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
+    return accum_export(a, host_sums, host_squares, host_stop);
+}
+
+extern "C" RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                                 const float* host_squares, const uint32_t* host_stop) {
+    if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    return accum_import(a, info, host_sums, host_squares, host_stop);
+}
+
+extern "C" RTW_API int rtw_accum_tile_stops(rtw_accum* a, uint32_t* host_stop) {
+    if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (!a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
+    HIP_TRY(hipSetDevice(a->g->device));
+    if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
+    if (a->tiles > 0) HIP_TRY(hipMemcpy(host_stop, a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_resolve_samples(rtw_accum* a, uint32_t* d_out, void* stream) {
+    return accum_resolve(a, (float*)d_out, (hipStream_t)stream, 2);
+}
+
+extern "C" RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_samples, void* stream_, int64_t* active_tiles,
+                                       int64_t* active_pixels) {
+    if (!a || !active_tiles || !active_pixels) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (!a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
+    if (a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the stop test needs samples >= 2");
+    if (min_samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "min_samples must be >= 2");
+    hipStream_t stream = (hipStream_t)stream_;
+    rtw_adapt_geom G;
+    if (rtw_adapt_geom_of(&a->p, &G) != 0 || (uint32_t)G.local_tiles != a->tiles)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
+    *active_tiles = 0;
+    *active_pixels = 0;
+    if (a->tiles == 0) return RTW_OK;
+    int rc = accum_enter(a, stream);
+    if (rc != RTW_OK) return rc;
+    const uint32_t waves = RTW_ADAPT_BLOCK / 64;
+    hipLaunchKernelGGL(adapt_tiles_kernel, dim3((a->tiles + waves - 1) / waves), dim3(RTW_ADAPT_BLOCK), 0, stream,
+                       (const float*)a->sums, (const float*)a->squares, G, a->info.samples, target, min_samples, a->tile_stop);
+    HIP_TRY(hipGetLastError());
+    rc = accum_leave(a, stream);
+    if (rc != RTW_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(a->h_stop.data(), a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    uint32_t active = 0;
+    int64_t pixels = 0;
+    for (uint32_t t = 0; t < a->tiles; ++t)
+        if (a->h_stop[t] == 0) {
+            ++active;
+            pixels += tile_pixels(a->info, t);
+        }
+    a->active = active;
+    *active_tiles = active;
+    *active_pixels = pixels;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_adapt_tiles_host(const float* sums, const float* squares, const rtw_render_params* params,
+                                            uint32_t samples, float target, uint32_t min_samples, uint32_t* tile_stop) {
+    if (!sums || !squares || !params || !tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (rtw_adapt_tiles(sums, squares, params, samples, target, min_samples, tile_stop) != 0)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the stop test needs samples >= 2, min_samples >= 2 and a frame's geometry");
+    return RTW_OK;
+}
+
+// The compaction kernel alone (tests): order (null: the identity) and stop on the host, n entries each;
+// out[n] gets the active tiles in order, *out_count their number.
+extern "C" RTW_API int rtw_debug_compact(int device, const uint32_t* order, const uint32_t* stop, uint32_t n, uint32_t* out,
+                                         uint32_t* out_count) {
+    if (!stop || !out || !out_count || n == 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument or n == 0");
+    HIP_TRY(hipSetDevice(device));
+    uint32_t* d = nullptr;  // [order n][stop n][out n][count 1]
+    const size_t nb = (size_t)n * sizeof(uint32_t);
+    HIP_TRY(hipMalloc(&d, 3 * nb + sizeof(uint32_t)));
+    hipError_t e = hipMemset(d, 0xFF, 3 * nb + sizeof(uint32_t));
+    if (e == hipSuccess && order) e = hipMemcpy(d, order, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + n, stop, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(compact_active_kernel, dim3(1), dim3(RTW_COMPACT_BLOCK), 0, nullptr, order ? (const uint32_t*)d : nullptr,
+                           (const uint32_t*)(d + n), n, d + 2 * (size_t)n, d + 3 * (size_t)n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d + 2 * (size_t)n, nb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_count, d + 3 * (size_t)n, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return rtw::fail(RTW_ERR_HIP, std::string("rtw_debug_compact: ") + hipGetErrorString(e));
     return RTW_OK;
 }
 

@@ -7,6 +7,12 @@ samples the image is bit-identical to `render` at samples_per_pixel = n1 + n2 + 
 reference at that spp.  With ``moments=True`` the accumulator also keeps per-channel sums of squares:
 `stderr()` is the standard error of each channel's mean and `noise()` one scalar for the partition.
 
+With ``adaptive=True`` (implies moments) the noise estimate also places the samples: `adapt(target)` stops
+every tile whose worst pixel's relative standard error is at most `target`, and `add` renders the active
+tiles only.  A stopped tile stays stopped; it holds, bit for bit, the pixels of `render` at
+samples_per_pixel = its own count (`tile_stops()`, `sample_counts()`), so the image stays exact tile by
+tile, with the stop map as part of the output.  `render_adaptive` is the loop.
+
 The reference's thread_count > 1 splits a frame's samples into planes by the *final* spp
 (split_work_tasks, rendering.rs:222-237), so a prefix of such a frame is not a frame: accumulators
 render thread_count 1 only.
@@ -36,7 +42,9 @@ _HEADER = {**{n: np.uint32 for n in _U32}, **{n: np.int32 for n in _I32}, **{n: 
 @dataclass
 class AccumState:
     """One accumulator's exported state: the fields of rtw_accum_info, the per-slot sums and, with
-    moments, the sums of squares (float32, shape (slots, 3); padding slots of edge tiles hold zeros)."""
+    moments, the sums of squares (float32, shape (slots, 3); padding slots of edge tiles hold zeros);
+    of an adaptive accumulator also the stop map (uint32, shape (tiles,), tiles = slots / (tile_width *
+    tile_height): 0 = active, else the sample count the tile stopped at)."""
 
     version: int
     flags: int
@@ -55,17 +63,28 @@ class AccumState:
     slots: int
     sums: np.ndarray
     squares: np.ndarray | None = None
+    tile_stop: np.ndarray | None = None
 
     def header(self) -> dict:
         return {n: int(getattr(self, n)) for n in _HEADER}
 
+    @property
+    def tiles(self) -> int:
+        """Local tiles of the partition (entries of the stop map)."""
+        return int(self.slots) // (int(self.tile_width) * int(self.tile_height))
+
     def save(self, path) -> None:
-        """One .npz of plain arrays (numpy.savez): a 0-d array per header field, `sums`, and `squares`
-        when the accumulator kept moments."""
+        """One .npz of plain arrays (numpy.savez): a 0-d array per header field, `sums`, `squares`
+        when the accumulator kept moments, and `tile_stop` when it was adaptive."""
         arrays = {n: np.asarray(getattr(self, n), dtype=t) for n, t in _HEADER.items()}
         arrays["sums"] = np.ascontiguousarray(self.sums, np.float32)
         if self.squares is not None:
             arrays["squares"] = np.ascontiguousarray(self.squares, np.float32)
+        if self.tile_stop is not None:
+            stop = np.asarray(self.tile_stop)
+            if stop.dtype != np.uint32 or stop.shape != (self.tiles,):
+                raise ValueError("tile_stop is not uint32 of shape (tiles,)")
+            arrays["tile_stop"] = np.ascontiguousarray(stop)
         with open(path, "wb") as f:
             np.savez(f, **arrays)
 
@@ -75,7 +94,7 @@ class AccumState:
         arrays `save` writes is refused."""
         with np.load(path, allow_pickle=False) as z:
             names = set(z.files)
-            known = set(_HEADER) | {"sums", "squares"}
+            known = set(_HEADER) | {"sums", "squares", "tile_stop"}
             if names - known:
                 raise ValueError(f"not an accumulator checkpoint: unexpected entries {sorted(names - known)}")
             missing = (set(_HEADER) | {"sums"}) - names
@@ -95,7 +114,12 @@ class AccumState:
                 if a.dtype != np.float32 or a.shape != (vals["slots"], 3):
                     raise ValueError(f"accumulator checkpoint: {n} is not float32 of shape (slots, 3)")
                 arrays[n] = a
-        return cls(**vals, sums=arrays["sums"], squares=arrays.get("squares"))
+            if "tile_stop" in names:
+                a = z["tile_stop"]
+                if a.dtype != np.uint32 or a.shape != (vals["slots"] // max(1, vals["tile_width"] * vals["tile_height"]),):
+                    raise ValueError("accumulator checkpoint: tile_stop is not uint32 of shape (tiles,)")
+                arrays["tile_stop"] = a
+        return cls(**vals, sums=arrays["sums"], squares=arrays.get("squares"), tile_stop=arrays.get("tile_stop"))
 
 
 assert [f.name for f in fields(AccumState)][:len(_HEADER)] == [n for n, _ in N.AccumInfo._fields_]
@@ -103,6 +127,10 @@ assert [f.name for f in fields(AccumState)][:len(_HEADER)] == [n for n, _ in N.A
 
 def _f32p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _u32p(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
 class Accumulator:
@@ -114,17 +142,18 @@ class Accumulator:
     def __init__(self, world: World | DeviceWorld, size: Size2i, max_depth: int,
                  render_mode: RenderMode = RenderMode.Default, *, seed: int = DEFAULT_SEED, device: int = 0,
                  tile: tuple[int, int] = (8, 8), part: tuple[int, int] = (0, 1), layout: int = N.LAYOUT_IMAGE,
-                 moments: bool = False, thread_count: int = 1):
+                 moments: bool = False, adaptive: bool = False, thread_count: int = 1):
         self._h = None
         self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
         self.device = self.dworld.device
         self.size = size
-        self.moments = bool(moments)
+        self.adaptive = bool(adaptive)
+        self.moments = bool(moments) or self.adaptive
         self.params = render_params(size, 0, max_depth, render_mode, seed, tile=tile, part=part, layout=layout,
                                     thread_count=thread_count)
         h = C.c_void_p()
-        check(lib().rtw_accum_create(self.dworld._h, C.byref(self.params), N.ACCUM_MOMENTS if moments else 0,
-                                     C.byref(h)))
+        flags = (N.ACCUM_MOMENTS if self.moments else 0) | (N.ACCUM_ADAPTIVE if self.adaptive else 0)
+        check(lib().rtw_accum_create(self.dworld._h, C.byref(self.params), flags, C.byref(h)))
         self._h = h
         self._out = None
 
@@ -147,7 +176,7 @@ class Accumulator:
 
     @property
     def samples(self) -> int:
-        """Samples per pixel added so far."""
+        """Samples per pixel added so far (adaptive: of the active tiles, the frontier)."""
         return int(self.info().samples)
 
     @property
@@ -155,7 +184,8 @@ class Accumulator:
         return int(self.info().slots)
 
     def add(self, n: int, stream_ptr: int | None = None) -> None:
-        """Renders the next `n` samples of every pixel and adds them (asynchronous on `stream_ptr`)."""
+        """Renders the next `n` samples of every pixel and adds them (asynchronous on `stream_ptr`).  Adaptive:
+        of the pixels of the active tiles only; with none active the call does nothing."""
         if n < 0:
             raise ValueError("n must be >= 0")
         check(lib().rtw_accum_add(self._h, n, C.c_void_p(stream_ptr or 0)))
@@ -167,16 +197,16 @@ class Accumulator:
     def _rows(self) -> int:
         return self.slots if self.params.layout == N.LAYOUT_TILES else self.size.width * self.size.height
 
-    def _resolved(self, fn) -> np.ndarray:
+    def _resolved(self, fn, channels: int = 3, dtype=None) -> np.ndarray:
         import torch
 
         dev = torch.device("cuda", self.device)
         # (zeros: with part_count > 1 an IMAGE-layout resolve leaves the other partitions' pixels alone)
-        out = torch.zeros(self._rows() * 3, dtype=torch.float32, device=dev)
+        out = torch.zeros(self._rows() * channels, dtype=dtype or torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev)
         check(fn(self._h, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
         stream.synchronize()
-        return out.cpu().numpy().reshape(-1, 3)
+        return out.cpu().numpy().reshape(-1, channels)
 
     def image(self) -> np.ndarray:
         """The image so far on the host: (W*H, 3) f32 (LAYOUT_IMAGE) or (slots, 3) (LAYOUT_TILES)."""
@@ -193,12 +223,43 @@ class Accumulator:
         check(lib().rtw_accum_noise(self._h, C.c_void_p(stream_ptr or 0), C.byref(v), C.byref(n)))
         return v.value, n.value
 
+    def sample_counts(self) -> np.ndarray:
+        """The samples each pixel holds (its tile's count), uint32, laid out as `image()` with one channel;
+        padding slots of a tile buffer hold 0."""
+        import torch
+
+        return self._resolved(lib().rtw_accum_resolve_samples, 1, torch.int32).view(np.uint32)
+
+    @property
+    def tiles(self) -> int:
+        """Local tiles of the partition (entries of the stop map)."""
+        return self.slots // (self.params.tile_width * self.params.tile_height)
+
+    def adapt(self, target: float, min_samples: int = 16, stream_ptr: int | None = None) -> tuple[int, int]:
+        """Stops every active tile whose worst pixel has a relative standard error (the per-pixel value of
+        `noise()`) of at most `target`, once the accumulator holds `min_samples` samples.  Returns (active
+        tiles, active pixels) after the decision (adaptive, samples >= 2, min_samples >= 2)."""
+        t, p = C.c_int64(), C.c_int64()
+        check(lib().rtw_accum_adapt(self._h, target, min_samples, C.c_void_p(stream_ptr or 0), C.byref(t), C.byref(p)))
+        return t.value, p.value
+
+    def tile_stops(self) -> np.ndarray:
+        """The stop map: per local tile 0 (active) or the sample count it stopped at (uint32, shape (tiles,))."""
+        stop = np.zeros(self.tiles, np.uint32)
+        check(lib().rtw_accum_tile_stops(self._h, _u32p(stop)))
+        return stop
+
     def state(self) -> AccumState:
         i = self.info()
         sums = np.zeros((i.slots, 3), np.float32)
         squares = np.zeros((i.slots, 3), np.float32) if self.moments else None
-        check(lib().rtw_accum_export(self._h, _f32p(sums), _f32p(squares) if squares is not None else None))
-        return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, sums=sums, squares=squares)
+        stop = None
+        if self.adaptive:
+            stop = np.zeros(self.tiles, np.uint32)
+            check(lib().rtw_accum_export_adaptive(self._h, _f32p(sums), _f32p(squares), _u32p(stop)))
+        else:
+            check(lib().rtw_accum_export(self._h, _f32p(sums), _f32p(squares) if squares is not None else None))
+        return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, sums=sums, squares=squares, tile_stop=stop)
 
     def load_state(self, state: AccumState) -> None:
         """Continue `state`'s frame here.  Raises RtwError naming the field when the state belongs to another
@@ -210,7 +271,14 @@ class Accumulator:
         squares = None if state.squares is None else np.ascontiguousarray(state.squares, np.float32)
         if sums.size != 3 * state.slots or (squares is not None and squares.size != sums.size):
             raise ValueError("state arrays do not hold 3 * slots floats")
-        check(lib().rtw_accum_import(self._h, C.byref(i), _f32p(sums), _f32p(squares) if squares is not None else None))
+        sq = _f32p(squares) if squares is not None else None
+        if state.tile_stop is not None:
+            stop = np.ascontiguousarray(state.tile_stop, np.uint32)
+            if stop.shape != (self.tiles,):
+                raise ValueError("state.tile_stop does not hold one entry per tile")
+            check(lib().rtw_accum_import_adaptive(self._h, C.byref(i), _f32p(sums), sq, _u32p(stop)))
+        else:  # (refused by an adaptive accumulator: its state includes the stop map)
+            check(lib().rtw_accum_import(self._h, C.byref(i), _f32p(sums), sq))
 
 
 def world_fingerprint(world: World) -> int:
@@ -247,5 +315,30 @@ def render_to_noise(size: Size2i, max_depth: int, world, target: float, max_samp
                 if noise <= target:
                     break
         return acc.image(), acc.samples, noise
+    finally:
+        acc.release()
+
+
+def render_adaptive(size: Size2i, max_depth: int, world, target: float, max_samples: int, min_samples: int = 16,
+                    batch: int = 16, **kw):
+    """Adds `batch` samples at a time (the last batch cut to `max_samples`) to the active tiles and, from
+    `min_samples` on, stops the tiles whose worst pixel's relative standard error is at most `target`
+    (`Accumulator.adapt`), until no tile is active or samples == max_samples.  Returns (image, sample_counts,
+    info): info = {"samples": the frontier, "samples_rendered": the sum of the counts over the owned pixels,
+    "active_tiles", "noise"}.  Every tile of the image equals `render` at its own count."""
+    if max_samples < 2 or batch < 1 or min_samples < 2:
+        raise ValueError("max_samples and min_samples must be >= 2 and batch >= 1")
+    kw["adaptive"] = True
+    acc = Accumulator(world, size, max_depth, **kw)
+    try:
+        active = acc.tiles
+        while active > 0 and acc.samples < max_samples:
+            acc.add(min(batch, max_samples - acc.samples))
+            if acc.samples >= min_samples:
+                active = acc.adapt(target, min_samples)[0]
+        counts = acc.sample_counts()
+        info = {"samples": acc.samples, "samples_rendered": int(counts.astype(np.int64).sum()), "active_tiles": active,
+                "noise": acc.noise()[0]}
+        return acc.image(), counts, info
     finally:
         acc.release()
