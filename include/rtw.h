@@ -439,6 +439,38 @@ RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* hos
 RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                       const float* host_squares, const uint32_t* host_tile_stop);
 
+/* ---- preview denoiser ---------------------------------------------------------------------- */
+/* A variance-guided a-trous filter for accumulator previews, built on nothing but images:
+ * a colour image, the standard error of its channels (rtw_accum_resolve_stderr) and an optional guide of
+ * 0..4 channels per pixel (a RTW_MODE_NORMALS frame, say), all RTW_LAYOUT_IMAGE.  The arithmetic is a fixed
+ * f32 expression (include/rtw_denoise.h): the device kernels, rtw_denoise_host and a numpy restatement give
+ * the same bits.  Pixels whose colour sum, variance or guide is not finite are left out: no other pixel reads
+ * them and they pass through bit for bit.  A preview filter: the exact image stays rtw_accum_resolve's. */
+typedef struct rtw_denoise_params {
+    int32_t width, height;        /* >= 2 */
+    int32_t iterations;           /* 1..6: level i taps at a step of 1 << i pixels */
+    int32_t guide_channels;       /* 0..4 */
+    float sigma_l, sigma_g;       /* > 0: luminance tolerance in standard deviations; guide distance cut-off */
+    int32_t reserved0, reserved1; /* 0 */
+} rtw_denoise_params;
+typedef struct rtw_denoiser rtw_denoiser;
+/* Allocates the scratch of a width x height filter on `device`: two record buffers and the guide buffer,
+ * 48 bytes per pixel. */
+RTW_API int rtw_denoiser_create(int device, int32_t width, int32_t height, rtw_denoiser** out);
+RTW_API int rtw_denoiser_release(rtw_denoiser* d);
+/* Runs the filter on device buffers: d_color and d_stderr W*H*3 floats, d_guide W*H*guide_channels floats
+ * (NULL only when guide_channels is 0), d_out W*H*3 floats (may be d_color: the prep pass copies out of the
+ * inputs first), d_out_variance W*H floats or NULL (the variance of each pixel's filtered luminance estimate,
+ * NaN for pixels that were left out).  RTW_ERR_INVALID_ARGUMENT, with a message naming the field, for a size
+ * other than the denoiser's, iterations outside 1..6, guide_channels outside 0..4, a non-positive or
+ * non-finite sigma, non-zero reserved fields and null pointers.  Asynchronous. */
+RTW_API int rtw_denoiser_run(rtw_denoiser* d, const rtw_denoise_params* params, const float* d_color,
+                             const float* d_stderr, const float* d_guide, float* d_out, float* d_out_variance,
+                             void* stream);
+/* The same filter on host arrays, without a GPU (the same refusals, but any size >= 2 x 2). */
+RTW_API int rtw_denoise_host(const rtw_denoise_params* params, const float* color, const float* std_err,
+                             const float* guide, float* out, float* out_variance);
+
 /* Floats needed by one partition's RTW_LAYOUT_TILES buffer (tiles * tile_w * tile_h * 3). */
 RTW_API int rtw_partition_floats(const rtw_render_params* params, int64_t* floats);
 /* Scatters part_count gathered tile buffers (each padded to `stride_floats`) into a W*H*3

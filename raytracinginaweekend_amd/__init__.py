@@ -6,6 +6,7 @@ include/rtw.h).  This package is its Python face, mirroring the reference's inte
 Camera.build()..., WorldBuilder / NodeBuilder, demo worlds, rendering.render(...).
 """
 from . import image_io
+from .denoise import Denoiser, denoise_host
 from .progressive import (
     Accumulator,
     AccumState,
@@ -45,6 +46,7 @@ __all__ = [
     "BackgroundColor",
     "Camera",
     "DEMO_WORLDS",
+    "Denoiser",
     "DeviceWorld",
     "MultiDeviceWorld",
     "NodeBuilder",
@@ -55,6 +57,7 @@ __all__ = [
     "World",
     "WorldBuilder",
     "demo_world",
+    "denoise_host",
     "device_count",
     "load_obj_mesh",
     "render",

@@ -214,6 +214,19 @@ class AccumInfo(C.Structure):  # rtw_accum_info: fixed-width fields, no padding 
     ]
 
 
+class DenoiseParams(C.Structure):  # rtw_denoise_params
+    _fields_ = [
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("iterations", C.c_int32),
+        ("guide_channels", C.c_int32),
+        ("sigma_l", C.c_float),
+        ("sigma_g", C.c_float),
+        ("reserved0", C.c_int32),
+        ("reserved1", C.c_int32),
+    ]
+
+
 class CameraSpec(C.Structure):
     _fields_ = [
         ("fov_mode", C.c_int32),
@@ -299,6 +312,10 @@ _SIGS = {
     "rtw_accum_export_adaptive": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtw_accum_import_adaptive": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_uint32)]),
+    "rtw_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "rtw_denoiser_release": (C.c_int, [_P]),
+    "rtw_denoiser_run": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P]),
+    "rtw_denoise_host": (C.c_int, [C.POINTER(DenoiseParams)] + [C.POINTER(C.c_float)] * 5),
     "rtw_debug_compact": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rtw_partition_floats": (C.c_int, [C.POINTER(RenderParams), C.POINTER(C.c_int64)]),

@@ -144,6 +144,7 @@ class Accumulator:
                  tile: tuple[int, int] = (8, 8), part: tuple[int, int] = (0, 1), layout: int = N.LAYOUT_IMAGE,
                  moments: bool = False, adaptive: bool = False, thread_count: int = 1):
         self._h = None
+        self._denoiser = None  # made by the first denoised()
         self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
         self.device = self.dworld.device
         self.size = size
@@ -161,6 +162,9 @@ class Accumulator:
         if getattr(self, "_h", None) is not None and self._h.value:
             lib().rtw_accum_release(self._h)
             self._h = None
+        if getattr(self, "_denoiser", None) is not None:
+            self._denoiser.release()
+            self._denoiser = None
         self._out = None
 
     def __del__(self):
@@ -215,6 +219,56 @@ class Accumulator:
     def stderr(self) -> np.ndarray:
         """The standard error of each channel's mean, laid out as `image()` (moments, samples >= 2)."""
         return self._resolved(lib().rtw_accum_resolve_stderr)
+
+    def _resolved_device(self, fn):
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        out = torch.zeros((self.size.width * self.size.height, 3), dtype=torch.float32, device=dev)
+        check(fn(self._h, C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def denoised(self, guide=None, **options):
+        """A denoised preview of the image so far: (W*H, 3) f32 on the host (with variance=True also the (W*H,)
+        variance of each filtered pixel).  Resolves the image and `stderr()` on the device and runs a cached
+        `Denoiser` on them (denoise.py; options: iterations, sigma_l, sigma_g, variance).  `guide` is an
+        array or device tensor of shape (W*H, 1..4), or another Accumulator of this size and device whose image
+        is taken -- one in `RenderMode.Normals`, say.  Needs moments=True and samples >= 2.  Non-destructive: the
+        sums are only read, `image()` stays the exact image and further adds continue the frame.
+
+        A filter needs the whole image: an accumulator with LAYOUT_TILES or part != (0, 1) raises ValueError.
+        Rank users gather the image and the standard error and call `Denoiser.run` on rank 0."""
+        import torch
+
+        from .denoise import Denoiser
+
+        if self.params.layout != N.LAYOUT_IMAGE:
+            raise ValueError("denoised() needs the whole image: the accumulator's layout is LAYOUT_TILES")
+        if (self.params.part_index, max(1, self.params.part_count)) != (0, 1):
+            raise ValueError("denoised() needs the whole image: the accumulator holds one partition of it "
+                             "(gather the image and the standard error and call Denoiser.run on rank 0)")
+        if not self.moments:
+            raise ValueError("denoised() needs an accumulator with moments=True")
+        if self.samples < 2:
+            raise ValueError("denoised() needs samples >= 2")
+        dev = torch.device("cuda", self.device)
+        if isinstance(guide, Accumulator):
+            if (guide.size.width, guide.size.height) != (self.size.width, self.size.height) or guide.device != self.device:
+                raise ValueError("the guide accumulator has another size or device")
+            if guide.params.layout != N.LAYOUT_IMAGE or (guide.params.part_index, max(1, guide.params.part_count)) != (0, 1):
+                raise ValueError("the guide accumulator does not hold the whole image")
+            guide = guide._resolved_device(lib().rtw_accum_resolve)
+        elif guide is not None and not hasattr(guide, "data_ptr"):
+            guide = torch.from_numpy(np.ascontiguousarray(guide, np.float32)).to(dev)
+        if self._denoiser is None:
+            self._denoiser = Denoiser(self.size, self.device)
+        color = self._resolved_device(lib().rtw_accum_resolve)
+        se = self._resolved_device(lib().rtw_accum_resolve_stderr)
+        res = self._denoiser.run_device(color, se, guide, color, **options)
+        torch.cuda.current_stream(dev).synchronize()
+        if isinstance(res, tuple):
+            return res[0].cpu().numpy(), res[1].cpu().numpy()
+        return res.cpu().numpy()
 
     def noise(self, stream_ptr: int | None = None) -> tuple[float, int]:
         """(mean over the pixels of (se_r + se_g + se_b) / (mean_r + mean_g + mean_b + 0.01), pixels
