@@ -439,6 +439,57 @@ RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* hos
 RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                       const float* host_squares, const uint32_t* host_tile_stop);
 
+/* ---- first-hit AOVs ------------------------------------------------------------------------- */
+/* An AOV accumulator keeps, per pixel of the whole image, running sums of what the camera rays hit first:
+ * albedo, normal and depth.  An AOV sample is one camera ray and one closest hit, no bounce;
+ * it draws the (seed, pixel, sample) stream of the colour sample, so AOV sample s describes the primary ray of
+ * colour sample s: same jitter, lens point, time and volume draws.  Per pixel pix = y * W + x and sample s:
+ *   rng = rtw_sample_stream(rtw_seed_key(seed), pix, s); the two jitter draws; Camera::ray; the reference's
+ *   closest hit over [0.001, inf) with the rng carried on.
+ *   hit:  a = (1, 1, 1) for a dielectric, else 0 + 1 * the material's texture at the hit (every other kind, a
+ *         DiffuseLight's emit texture included); nrm = (n + 1) * 0.5 (the RTW_MODE_NORMALS expression);
+ *         depth_sum = depth_sum + t; hits += 1.
+ *   miss: a = (1, 1, 1); nrm = the ray's background, as RTW_MODE_NORMALS gives it.
+ *   sum = sum + value per channel, in sample order, from +0.
+ * Resolve: albedo and normal sum / (float)samples; depth hits ? depth_sum / (float)hits : 0 (finite on a miss:
+ * it can serve as a guide channel).  Adds of n1, n2, ... give the bits of one add of n1 + n2 + ...; the normal
+ * image is bit-identical to a RTW_MODE_NORMALS frame of the same seed and samples_per_pixel; the albedo image
+ * is the reference's radiance of the world's emissive twin (every material a DiffuseLight of its own texture,
+ * a dielectric one of solid white, no light rect, background solid white, max_depth 2).
+ *
+ * rtw_aov_create reads width, height and seed from params, and refuses, naming the field: RTW_LAYOUT_TILES,
+ * part_count > 1 and thread_count > 1 (RTW_ERR_UNSUPPORTED: the pass covers the whole image, in
+ * RTW_LAYOUT_IMAGE); channels 0 or with an unknown bit and reserved0 != 0 (RTW_ERR_INVALID_ARGUMENT).  The
+ * params are checked before the world, and nothing is allocated or launched for params it refuses.  The
+ * accumulator owns its sums and touches none of the world's scratch: colour accumulators, one-shot frames and
+ * AOV accumulators of one world interleave freely.  Calls on one AOV accumulator are ordered by the caller
+ * (one stream, or events).  rtw_world_release takes its device state as it takes a colour accumulator's. */
+#define RTW_AOV_ALBEDO 1u
+#define RTW_AOV_NORMAL 2u
+#define RTW_AOV_DEPTH 4u
+typedef struct rtw_aov rtw_aov;
+typedef struct rtw_aov_info { /* all fields fixed-width, no padding */
+    uint32_t version;  /* 1 */
+    uint32_t channels; /* RTW_AOV_* */
+    int32_t width, height;
+    uint32_t samples;  /* samples added so far, per pixel */
+    uint32_t reserved; /* 0 */
+    uint64_t seed;
+    uint64_t world_fingerprint; /* rtw_world_fingerprint of the uploaded world */
+} rtw_aov_info;
+RTW_API int rtw_aov_create(rtw_gpu_world* gw, const rtw_render_params* params, uint32_t channels, rtw_aov** out);
+RTW_API int rtw_aov_release(rtw_aov* a);
+/* Traces samples [samples, samples + n) of every pixel and adds them.  Asynchronous on `stream`, one launch.
+ * n == 0 does nothing; samples + n beyond 32 bits is RTW_ERR_INVALID_ARGUMENT. */
+RTW_API int rtw_aov_add(rtw_aov* a, uint32_t n_samples, void* stream);
+RTW_API int rtw_aov_get_info(rtw_aov* a, rtw_aov_info* out); /* host bookkeeping, no sync */
+/* One channel (exactly one RTW_AOV_* bit) into device buffer d_out, RTW_LAYOUT_IMAGE: W*H*3 floats for albedo
+ * and normal, W*H for depth.  RTW_ERR_INVALID_ARGUMENT for a channel the accumulator does not hold and at 0
+ * samples.  Non-destructive, asynchronous. */
+RTW_API int rtw_aov_resolve(rtw_aov* a, uint32_t channel, float* d_out, void* stream);
+/* The samples of each pixel that hit something: W*H uint32_t.  Any accumulator, at any point.  Asynchronous. */
+RTW_API int rtw_aov_hits(rtw_aov* a, uint32_t* d_out, void* stream);
+
 /* ---- preview denoiser ---------------------------------------------------------------------- */
 /* A variance-guided a-trous filter for accumulator previews, built on nothing but images:
  * a colour image, the standard error of its channels (rtw_accum_resolve_stderr) and an optional guide of
@@ -470,6 +521,18 @@ RTW_API int rtw_denoiser_run(rtw_denoiser* d, const rtw_denoise_params* params, 
 /* The same filter on host arrays, without a GPU (the same refusals, but any size >= 2 x 2). */
 RTW_API int rtw_denoise_host(const rtw_denoise_params* params, const float* color, const float* std_err,
                              const float* guide, float* out, float* out_variance);
+/* Albedo demodulation: the same calls plus an albedo image (W*H*3 floats, RTW_LAYOUT_IMAGE; a
+ * resolved RTW_AOV_ALBEDO channel, say).  The filter runs on colour / D and standard error / D with
+ * D_c = albedo_c >= 1/64 ? albedo_c : 1/64, and the output is the filtered value times D: a texture's contrast
+ * is divided out before the filter compares neighbours and put back after it (include/rtw_denoise.h has the
+ * order).  A pixel with a non-finite albedo channel is left out like one with a non-finite guide, and every
+ * pixel that is left out returns its input colour bit for bit.  The variance output is that of the
+ * demodulated luminance estimate, (r/D_r + g/D_g) + b/D_b.  albedo == NULL: exactly the calls above. */
+RTW_API int rtw_denoiser_run_albedo(rtw_denoiser* d, const rtw_denoise_params* params, const float* d_color,
+                                    const float* d_stderr, const float* d_guide, const float* d_albedo, float* d_out,
+                                    float* d_out_variance, void* stream);
+RTW_API int rtw_denoise_host_albedo(const rtw_denoise_params* params, const float* color, const float* std_err,
+                                    const float* guide, const float* albedo, float* out, float* out_variance);
 
 /* Floats needed by one partition's RTW_LAYOUT_TILES buffer (tiles * tile_w * tile_h * 3). */
 RTW_API int rtw_partition_floats(const rtw_render_params* params, int64_t* floats);

@@ -33,6 +33,15 @@
  *
  * The padded guide channels are zeros, so their d is +0 and d2 + d * d == d2 whatever d2 holds: summing 4
  * channels (the kernel) and gc channels give the same bits.
+ *
+ * Albedo demodulation (rtw_denoiser_run_albedo / rtw_denoise_host_albedo): with an albedo image
+ * A (W*H*3) the filter above runs unchanged between a pre-step and a post-step.  Per pixel p and channel c:
+ *   D_c = A_c >= 1/64 ? A_c : 1/64;  C'_c = C_c / D_c;  E'_c = E_c / D_c      (IEEE divisions)
+ *   Prep reads (C', E', G) for (C, E, G) -- its 3 x 3 window included -- and ok_p also needs every albedo
+ *   channel of p to be finite.
+ * Output: F_c * D_c for a pixel with ok_p (F the last records' rgb), else the input C_c bit for bit.  The
+ * variance output is the last records' w as before: the variance of the demodulated luminance estimate
+ * (C'_r + C'_g) + C'_b, NaN for pixels that were left out.  Without A nothing changes, bit for bit.
  */
 #ifndef RTW_DENOISE_H
 #define RTW_DENOISE_H
@@ -114,6 +123,66 @@ RTW_HD rtw_denoise_rec rtw_denoise_prep_pixel(const float* C, const float* E, co
     return r;
 }
 
+/* D of one albedo channel (a NaN gives 1/64; such a pixel is left out anyway) */
+RTW_HD float rtw_denoise_d(float a) { return a >= 0.015625f ? a : 0.015625f; }
+
+/* m_p with an albedo image: the demodulated colour of pixel `at` into c[3], and the luminance variance of the
+ * demodulated pixel, NaN when the pixel is left out */
+RTW_HD float rtw_denoise_m_albedo(const float* C, const float* E, const float* G, const float* A, int32_t gc, size_t at,
+                                  float c[3]) {
+    const float* a = A + 3 * at;
+    const float d0 = rtw_denoise_d(a[0]), d1 = rtw_denoise_d(a[1]), d2 = rtw_denoise_d(a[2]);
+    c[0] = C[3 * at] / d0;
+    c[1] = C[3 * at + 1] / d1;
+    c[2] = C[3 * at + 2] / d2;
+    const float e0 = E[3 * at] / d0, e1 = E[3 * at + 1] / d1, e2 = E[3 * at + 2] / d2;
+    const float l = (c[0] + c[1]) + c[2];
+    const float vr = e0 * e0, vg = e1 * e1, vb = e2 * e2;
+    const float vl = (vr + vg) + vb;
+    int ok = rtw_denoise_finite(a[0]) && rtw_denoise_finite(a[1]) && rtw_denoise_finite(a[2]);
+    ok = ok && rtw_denoise_finite(l) && rtw_denoise_finite(vl);
+    for (int32_t ch = 0; ch < gc; ++ch) ok = ok && rtw_denoise_finite(G[(size_t)gc * at + (size_t)ch]);
+    return ok ? vl : rtw_denoise_nan();
+}
+
+/* the prep record of pixel (x, y) with an albedo image: rtw_denoise_prep_pixel on the demodulated inputs */
+RTW_HD rtw_denoise_rec rtw_denoise_prep_pixel_albedo(const float* C, const float* E, const float* G, const float* A,
+                                                     int32_t gc, int32_t W, int32_t H, int32_t x, int32_t y) {
+    const size_t at = (size_t)y * (size_t)W + (size_t)x;
+    float c[3], cq[3];
+    const int ok = rtw_denoise_finite(rtw_denoise_m_albedo(C, E, G, A, gc, at, c));
+    float sk = 0.0f, sv = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy) {
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int32_t qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const float m = rtw_denoise_m_albedo(C, E, G, A, gc, (size_t)qy * (size_t)W + (size_t)qx, cq);
+            if (!rtw_denoise_finite(m)) continue;
+            const float kk = rtw_denoise_k(dy) * rtw_denoise_k(dx);
+            sk = sk + kk;
+            sv = sv + kk * m;
+        }
+    }
+    rtw_denoise_rec r;
+    r.r = c[0];
+    r.g = c[1];
+    r.b = c[2];
+    r.w = ok ? sv / sk : rtw_denoise_nan();
+    return r;
+}
+
+/* The post-step of pixel `at`: the last record f times D where the pixel was in at prep, else the input colour.
+ * Prep marks a pixel it leaves out with w = NaN and a level hands such a record on as it is; a pixel that was in
+ * never gets a NaN w (sv / sk and s2 / (sw * sw) divide sums of non-negative terms by sk > 0 and sw >= 9/64: they
+ * may reach +inf, never NaN).  So f.w is NaN exactly for the pixels that were left out. */
+RTW_HD __attribute__((always_inline)) void rtw_denoise_remodulate(const float* C, const float* A, size_t at,
+                                                                  rtw_denoise_rec f, float o[3]) {
+    const int ok = f.w == f.w;
+    o[0] = ok ? f.r * rtw_denoise_d(A[3 * at]) : C[3 * at];
+    o[1] = ok ? f.g * rtw_denoise_d(A[3 * at + 1]) : C[3 * at + 1];
+    o[2] = ok ? f.b * rtw_denoise_d(A[3 * at + 2]) : C[3 * at + 2];
+}
+
 /* the guide of pixel `at`, padded with zeros */
 RTW_HD rtw_denoise_rec rtw_denoise_guide_pixel(const float* G, int32_t gc, size_t at) {
     rtw_denoise_rec g;
@@ -182,10 +251,11 @@ RTW_HD __attribute__((always_inline)) rtw_denoise_rec rtw_denoise_level_pixel(co
 
 /* The whole filter on host arrays, pixel after pixel: the host form of the device's three kernels.  `scratch`
  * holds RTW_DENOISE_SCRATCH_RECS * width * height records.  out may be color (the prep pass reads the inputs
- * first); out_variance may be NULL; guide may be NULL when guide_channels is 0.  0, or -1 for params
- * rtw_denoise_check refuses. */
-RTW_HD int rtw_denoise_image(const rtw_denoise_params* p, const float* color, const float* std_err, const float* guide,
-                             float* out, float* out_variance, rtw_denoise_rec* scratch) {
+ * first); out_variance may be NULL; guide may be NULL when guide_channels is 0; albedo may be NULL (no
+ * demodulation).  0, or -1 for params rtw_denoise_check refuses. */
+RTW_HD int rtw_denoise_image_albedo(const rtw_denoise_params* p, const float* color, const float* std_err,
+                                    const float* guide, const float* albedo, float* out, float* out_variance,
+                                    rtw_denoise_rec* scratch) {
     if (rtw_denoise_check(p) != 0) return -1;
     const int32_t W = p->width, H = p->height, gc = p->guide_channels;
     const size_t n = (size_t)W * (size_t)H;
@@ -196,7 +266,8 @@ RTW_HD int rtw_denoise_image(const rtw_denoise_params* p, const float* color, co
     for (int32_t y = 0; y < H; ++y) {
         for (int32_t x = 0; x < W; ++x) {
             const size_t at = (size_t)y * (size_t)W + (size_t)x;
-            src[at] = rtw_denoise_prep_pixel(color, std_err, guide, gc, W, H, x, y);
+            src[at] = albedo ? rtw_denoise_prep_pixel_albedo(color, std_err, guide, albedo, gc, W, H, x, y)
+                             : rtw_denoise_prep_pixel(color, std_err, guide, gc, W, H, x, y);
             G4[at] = rtw_denoise_guide_pixel(guide, gc, at);
         }
     }
@@ -210,12 +281,25 @@ RTW_HD int rtw_denoise_image(const rtw_denoise_params* p, const float* color, co
         dst = t;
     }
     for (size_t at = 0; at < n; ++at) {
-        out[3 * at] = src[at].r;
-        out[3 * at + 1] = src[at].g;
-        out[3 * at + 2] = src[at].b;
+        if (albedo) {  /* (reads the pixel's own inputs before writing it: out may be color) */
+            float o[3];
+            rtw_denoise_remodulate(color, albedo, at, src[at], o);
+            out[3 * at] = o[0];
+            out[3 * at + 1] = o[1];
+            out[3 * at + 2] = o[2];
+        } else {
+            out[3 * at] = src[at].r;
+            out[3 * at + 1] = src[at].g;
+            out[3 * at + 2] = src[at].b;
+        }
         if (out_variance) out_variance[at] = src[at].w;
     }
     return 0;
+}
+
+RTW_HD int rtw_denoise_image(const rtw_denoise_params* p, const float* color, const float* std_err, const float* guide,
+                             float* out, float* out_variance, rtw_denoise_rec* scratch) {
+    return rtw_denoise_image_albedo(p, color, std_err, guide, 0, out, out_variance, scratch);
 }
 
 #ifdef __cplusplus

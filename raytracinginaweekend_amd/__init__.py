@@ -6,6 +6,7 @@ include/rtw.h).  This package is its Python face, mirroring the reference's inte
 Camera.build()..., WorldBuilder / NodeBuilder, demo worlds, rendering.render(...).
 """
 from . import image_io
+from .aov import AovAccumulator, render_aov
 from .denoise import Denoiser, denoise_host
 from .progressive import (
     Accumulator,
@@ -42,6 +43,7 @@ from .world import (
 __all__ = [
     "AccumState",
     "Accumulator",
+    "AovAccumulator",
     "AssetSet",
     "BackgroundColor",
     "Camera",
@@ -61,6 +63,7 @@ __all__ = [
     "device_count",
     "load_obj_mesh",
     "render",
+    "render_aov",
     "render_devices",
     "render_adaptive",
     "render_params",

@@ -214,6 +214,22 @@ class AccumInfo(C.Structure):  # rtw_accum_info: fixed-width fields, no padding 
     ]
 
 
+AOV_ALBEDO, AOV_NORMAL, AOV_DEPTH = 1, 2, 4  # RTW_AOV_*
+
+
+class AovInfo(C.Structure):  # rtw_aov_info: fixed-width fields, no padding
+    _fields_ = [
+        ("version", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("samples", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("world_fingerprint", C.c_uint64),
+    ]
+
+
 class DenoiseParams(C.Structure):  # rtw_denoise_params
     _fields_ = [
         ("width", C.c_int32),
@@ -312,6 +328,14 @@ _SIGS = {
     "rtw_accum_export_adaptive": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtw_accum_import_adaptive": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_uint32)]),
+    "rtw_aov_create": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.POINTER(_P)]),
+    "rtw_aov_release": (C.c_int, [_P]),
+    "rtw_aov_add": (C.c_int, [_P, C.c_uint32, _P]),
+    "rtw_aov_get_info": (C.c_int, [_P, C.POINTER(AovInfo)]),
+    "rtw_aov_resolve": (C.c_int, [_P, C.c_uint32, _P, _P]),
+    "rtw_aov_hits": (C.c_int, [_P, _P, _P]),
+    "rtw_denoiser_run_albedo": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
+    "rtw_denoise_host_albedo": (C.c_int, [C.POINTER(DenoiseParams)] + [C.POINTER(C.c_float)] * 6),
     "rtw_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "rtw_denoiser_release": (C.c_int, [_P]),
     "rtw_denoiser_run": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P]),

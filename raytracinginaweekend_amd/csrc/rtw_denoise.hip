@@ -63,6 +63,37 @@ __global__ __launch_bounds__(RTW_DENOISE_BX* RTW_DENOISE_BY) void denoise_level_
     }
 }
 
+// the same with an albedo image (rtw_denoiser_run_albedo): prep on the demodulated inputs ...
+__global__ __launch_bounds__(RTW_DENOISE_BX* RTW_DENOISE_BY) void denoise_prep_albedo_kernel(
+    const float* __restrict__ color, const float* __restrict__ std_err, const float* __restrict__ guide,
+    const float* __restrict__ albedo, int gc, int W, int H, rtw_denoise_rec* __restrict__ rec,
+    rtw_denoise_rec* __restrict__ guide4) {
+    int x, y;
+    if (!denoise_lane_pixel(W, H, &x, &y)) return;
+    const size_t at = (size_t)y * (size_t)W + (size_t)x;
+    rec[at] = rtw_denoise_prep_pixel_albedo(color, std_err, guide, albedo, gc, W, H, x, y);
+    if (gc > 0) guide4[at] = rtw_denoise_guide_pixel(guide, gc, at);
+}
+
+// ... and the last level, which multiplies the albedo back in, or hands a pixel that was left out its input colour.
+// `out` may be `color` (hence no __restrict__ on the two): a lane reads its own pixel's inputs, then writes it.
+template <bool GUIDE>
+__global__ __launch_bounds__(RTW_DENOISE_BX* RTW_DENOISE_BY) void denoise_level_albedo_kernel(
+    const rtw_denoise_rec* __restrict__ src, const rtw_denoise_rec* __restrict__ guide4, const float* color,
+    const float* __restrict__ albedo, int W, int H, int step, float sigma_l, float inv_sg2, float* out,
+    float* __restrict__ out_variance) {
+    int x, y;
+    if (!denoise_lane_pixel(W, H, &x, &y)) return;
+    const size_t at = (size_t)y * (size_t)W + (size_t)x;
+    const rtw_denoise_rec f = rtw_denoise_level_pixel(src, guide4, GUIDE ? 4 : 0, W, H, x, y, step, sigma_l, inv_sg2);
+    float o[3];
+    rtw_denoise_remodulate(color, albedo, at, f, o);
+    out[3 * at] = o[0];
+    out[3 * at + 1] = o[1];
+    out[3 * at + 2] = o[2];
+    if (out_variance) out_variance[at] = f.w;
+}
+
 struct rtw_denoiser {
     int device = 0;
     int32_t width = 0, height = 0;
@@ -123,9 +154,9 @@ extern "C" RTW_API int rtw_denoiser_release(rtw_denoiser* d) {
     return RTW_OK;
 }
 
-extern "C" RTW_API int rtw_denoiser_run(rtw_denoiser* d, const rtw_denoise_params* params, const float* d_color,
-                                        const float* d_stderr, const float* d_guide, float* d_out, float* d_out_variance,
-                                        void* stream_) {
+extern "C" RTW_API int rtw_denoiser_run_albedo(rtw_denoiser* d, const rtw_denoise_params* params, const float* d_color,
+                                               const float* d_stderr, const float* d_guide, const float* d_albedo,
+                                               float* d_out, float* d_out_variance, void* stream_) {
     if (!d) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null denoiser");
     const int v = check_params(params);
     if (v != RTW_OK) return v;
@@ -146,8 +177,12 @@ extern "C" RTW_API int rtw_denoiser_run(rtw_denoiser* d, const rtw_denoise_param
                     (unsigned)((p.height + RTW_DENOISE_BY - 1) / RTW_DENOISE_BY));
     const bool guided = p.guide_channels > 0;
     const float inv_sg2 = rtw_denoise_inv_sg2(p.sigma_g);
-    hipLaunchKernelGGL(denoise_prep_kernel, grid, dim3(RTW_DENOISE_BX * RTW_DENOISE_BY), 0, stream, d_color, d_stderr,
-                       d_guide, (int)p.guide_channels, (int)p.width, (int)p.height, src, guide4);
+    if (d_albedo)
+        hipLaunchKernelGGL(denoise_prep_albedo_kernel, grid, dim3(RTW_DENOISE_BX * RTW_DENOISE_BY), 0, stream, d_color,
+                           d_stderr, d_guide, d_albedo, (int)p.guide_channels, (int)p.width, (int)p.height, src, guide4);
+    else
+        hipLaunchKernelGGL(denoise_prep_kernel, grid, dim3(RTW_DENOISE_BX * RTW_DENOISE_BY), 0, stream, d_color, d_stderr,
+                           d_guide, (int)p.guide_channels, (int)p.width, (int)p.height, src, guide4);
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < p.iterations; ++i) {
         const int step = 1 << i;
@@ -157,6 +192,15 @@ extern "C" RTW_API int rtw_denoiser_run(rtw_denoiser* d, const rtw_denoise_param
             else
                 launch_level<false, false>(grid, stream, src, guide4, p, step, inv_sg2, dst, nullptr, nullptr);
             std::swap(src, dst);
+        } else if (d_albedo) {
+            if (guided)
+                hipLaunchKernelGGL((denoise_level_albedo_kernel<true>), grid, dim3(RTW_DENOISE_BX * RTW_DENOISE_BY), 0, stream,
+                                   (const rtw_denoise_rec*)src, (const rtw_denoise_rec*)guide4, d_color, d_albedo,
+                                   (int)p.width, (int)p.height, step, p.sigma_l, inv_sg2, d_out, d_out_variance);
+            else
+                hipLaunchKernelGGL((denoise_level_albedo_kernel<false>), grid, dim3(RTW_DENOISE_BX * RTW_DENOISE_BY), 0, stream,
+                                   (const rtw_denoise_rec*)src, (const rtw_denoise_rec*)guide4, d_color, d_albedo,
+                                   (int)p.width, (int)p.height, step, p.sigma_l, inv_sg2, d_out, d_out_variance);
         } else if (guided) {
             launch_level<true, true>(grid, stream, src, guide4, p, step, inv_sg2, nullptr, d_out, d_out_variance);
         } else {
@@ -167,8 +211,14 @@ extern "C" RTW_API int rtw_denoiser_run(rtw_denoiser* d, const rtw_denoise_param
     return RTW_OK;
 }
 
-extern "C" RTW_API int rtw_denoise_host(const rtw_denoise_params* params, const float* color, const float* std_err,
-                                        const float* guide, float* out, float* out_variance) {
+extern "C" RTW_API int rtw_denoiser_run(rtw_denoiser* d, const rtw_denoise_params* params, const float* d_color,
+                                        const float* d_stderr, const float* d_guide, float* d_out, float* d_out_variance,
+                                        void* stream) {
+    return rtw_denoiser_run_albedo(d, params, d_color, d_stderr, d_guide, nullptr, d_out, d_out_variance, stream);
+}
+
+extern "C" RTW_API int rtw_denoise_host_albedo(const rtw_denoise_params* params, const float* color, const float* std_err,
+                                               const float* guide, const float* albedo, float* out, float* out_variance) {
     const int v = check_params(params);
     if (v != RTW_OK) return v;
     if (!color) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null color");
@@ -178,7 +228,12 @@ extern "C" RTW_API int rtw_denoise_host(const rtw_denoise_params* params, const 
     const size_t n = (size_t)params->width * (size_t)params->height;
     auto* scratch = (rtw_denoise_rec*)std::aligned_alloc(16, RTW_DENOISE_SCRATCH_RECS * n * sizeof(rtw_denoise_rec));
     if (!scratch) return rtw::fail(RTW_ERR_OUT_OF_MEMORY, "no host memory for the denoiser's scratch");
-    const int rc = rtw_denoise_image(params, color, std_err, guide, out, out_variance, scratch);
+    const int rc = rtw_denoise_image_albedo(params, color, std_err, guide, albedo, out, out_variance, scratch);
     std::free(scratch);
     return rc == 0 ? RTW_OK : rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad rtw_denoise_params");
+}
+
+extern "C" RTW_API int rtw_denoise_host(const rtw_denoise_params* params, const float* color, const float* std_err,
+                                        const float* guide, float* out, float* out_variance) {
+    return rtw_denoise_host_albedo(params, color, std_err, guide, nullptr, out, out_variance);
 }

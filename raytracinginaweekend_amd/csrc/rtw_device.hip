@@ -3305,6 +3305,208 @@ __global__ void encode_kernel(const float* img, int64_t n, uint8_t* out) {
     out[i] = rtw_f2u8_sat(v);
 }
 
+// ---------------------------------------------------------------------------------------------
+// first-hit AOVs (rtw_aov_*, rtw.h): albedo, normal and depth of the camera rays
+// ---------------------------------------------------------------------------------------------
+// One lane per pixel, a wave per 8 x 8 tile, the add's samples in a loop with the sums in registers.  Sample s
+// of pixel pix draws the stream (seed, pix, s) as the colour sample does (start_sample): jitter, camera ray,
+// then the closest hit over [0.001, inf) with the stream carried on (volume leaves draw from it).  The walk is
+// the reference's (hittable.rs:429-473): depth first over node_a / node_b, the near child by dir[axis] > 0,
+// t_end narrowed by every hit, node_pass (hit_cond AND the proximity cull, which changes no result) -- so the
+// hit is the reference's, ties included.  Every leaf and texture kind reads global memory (ShadeTabs with all
+// offsets -1, as the self-test kernels).  The per-lane stack is the block's dynamic LDS: `depth` entries per
+// lane, the reference tree's depth (upload refuses trees deeper than RTW_STACK).
+// The sums are SoA planes in slot order (slot = tile * 64 + lane): a wave stores 256 contiguous bytes per plane.
+// (Measured and dropped, profiles/LOG.md round 11: lanes that start their next sample while the wave's other rays
+// go on, the tree in LDS, node steps at a faster cadence than leaf steps.  None beat this loop.)
+#define RTW_AOV_BLOCK 256
+struct AovArgs {
+    DWorld w;
+    int32_t width, height, tiles_x;
+    uint32_t slots;         // tiles * 64: the stride of the SoA planes
+    uint32_t s_begin, n;    // this add's samples [s_begin, s_begin + n)
+    int32_t mk_world;
+    uint64_t seed_key;
+    float sx, sy;
+    rtw_uniform ux, uy;
+    float* albedo;          // 3 planes, or null
+    float* normal;          // 3 planes, or null
+    float* depth;           // 1 plane (the sum of t over the samples that hit), or null
+    uint32_t* hits;         // 1 plane
+    // the camera rays' per-tile leaf lists of this image (primary_lists_kernel, 8 x 8 tiles = the waves' tiles):
+    // per tile the listed leaves (RTW_BEAM_WALK: the tile walks) and pl_cap leaf indices; null: every tile walks
+    const int32_t* pl_count;
+    const int32_t* pl_list;
+    int32_t pl_cap;
+};
+__device__ __forceinline__ bool aov_slot_pixel(uint32_t slot, int32_t tiles_x, int32_t width, int32_t height, int32_t& px,
+                                               int32_t& py) {
+    const uint32_t tile = slot >> 6, in = slot & 63u;
+    const int32_t ty = (int32_t)(tile / (uint32_t)tiles_x), tx = (int32_t)(tile - (uint32_t)ty * (uint32_t)tiles_x);
+    px = tx * 8 + (int32_t)(in & 7u);
+    py = ty * 8 + (int32_t)(in >> 3);
+    return px < width && py < height;
+}
+// PL: the accumulator holds leaf lists (a kernel of its own: the list step's registers cost the walk-only worlds
+// a wave per SIMD, 97 VGPRs against 92)
+template <bool PL>
+__global__ __launch_bounds__(RTW_AOV_BLOCK) void aov_kernel(AovArgs A) {
+    const DWorld& w = A.w;
+    const uint32_t slot = blockIdx.x * RTW_AOV_BLOCK + threadIdx.x;
+    int32_t px, py;
+    if (!aov_slot_pixel(slot, A.tiles_x, A.width, A.height, px, py)) return;  // (no barrier below)
+    const uint32_t pix = (uint32_t)(py * A.width + px);
+    const float fx = (float)px * A.sx, fy = (float)py * A.sy;
+    const ShadeTabs S{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
+    int32_t* stack = reinterpret_cast<int32_t*>(smem) + threadIdx.x;
+    Stats st;
+    // (a fresh accumulator's planes hold +0: the first add starts from them too)
+    const size_t n = A.slots;
+    V3 alb = v3(0.0f, 0.0f, 0.0f), nrm = v3(0.0f, 0.0f, 0.0f);
+    float dsum = 0.0f;
+    uint32_t hits = A.hits[slot];
+    if (A.albedo) alb = v3(A.albedo[slot], A.albedo[n + slot], A.albedo[2 * n + slot]);
+    if (A.normal) nrm = v3(A.normal[slot], A.normal[n + slot], A.normal[2 * n + slot]);
+    if (A.depth) dsum = A.depth[slot];
+    for (uint32_t k = 0; k < A.n; ++k) {
+        rtw_xoro rng = rtw_sample_stream(A.seed_key, pix, A.s_begin + k);
+        const float jx = d_uniform_sample(A.ux, &rng);
+        const float jy = d_uniform_sample(A.uy, &rng);
+        const Ray ray = camera_ray(w.wc->cam, rng, fx + jx, fy + jy);
+        const RayPre rp = ray_pre(ray, A.mk_world != 0);
+        const uint32_t sgn = (ray.d.x > 0.0f ? 1u : 0u) | (ray.d.y > 0.0f ? 2u : 0u) | (ray.d.z > 0.0f ? 4u : 0u);
+        float te = F32_INF;
+        int32_t found = -1, node = w.root, sp = 0;
+        bool live = true;
+        // A tile with a leaf list (rtw_beam.h; plain-sphere worlds): the list holds every leaf a camera ray of
+        // the tile can hit, so the closest root over it is the closest root over all leaves -- the megakernel's
+        // step for camera rays (render_body's PL), with its proof that this is the reference's answer (§5.2): no
+        // second leaf at exactly that root, and the leaf's parent box in the reference tree passes hit_cond at
+        // te = succ(t), so the reference DFS reaches the leaf.  An empty list is a miss.  A tie, a failed proof, a
+        // ray outside the exact fast division or a tile without a list takes the walk below.
+        if (PL) {
+            const int32_t n_list = A.pl_count[slot >> 6];
+            if (n_list >= 0 && rp.fast) {
+                const int32_t* __restrict__ L = A.pl_list + (size_t)(slot >> 6) * (uint32_t)A.pl_cap;
+                float ts = F32_INF;  // succ(closest t) once a leaf is found
+                int32_t f = -1;
+                bool tie = false;
+                for (int32_t j = 0; j < n_list; ++j) {
+                    const int32_t leaf = L[j];
+                    float t;
+                    if (sphere_t(w.leaf_fast[leaf], ray, 0.001f, ts, t)) {  // (sah_take)
+                        const bool same = f >= 0 && t == __int_as_float(__float_as_int(ts) - 1);
+                        tie = same ? (tie || f != leaf) : false;
+                        ts = same ? ts : __int_as_float(__float_as_int(t) + 1);
+                        f = same ? f : leaf;
+                    }
+                }
+                bool ok = !tie;
+                if (f >= 0)
+                    ok = ok && box_hit_cond_fast(w.leaf_box[2 * f], w.leaf_box[2 * f + 1], ray, RayPre{rp.inv, true}, 0.001f, ts);
+                if (ok) {
+                    live = false;
+                    found = f;
+                    if (f >= 0) te = __int_as_float(__float_as_int(ts) - 1);
+                }
+            }
+        }
+        while (live) {
+            if (node < 0) {  // a leaf is never box-tested (hittable.rs:436-437)
+                const int32_t leaf = -1 - node;
+                const float4 rec = w.leaf_fast[leaf];
+                float t;
+                bool hit;
+                if (rec.w == rec.w) {  // a plain sphere
+                    hit = sphere_t(rec, ray, 0.001f, te, t);
+                } else if (__float_as_int(rec.x) == 2) {  // a plain rect
+                    V3 pos;
+                    hit = rect_t(load_rect(w, S, __float_as_int(rec.y)), ray, 0.001f, te, t, pos);
+                } else if (__float_as_int(rec.x) == 1) {  // a plain triangle
+                    hit = tri_test(load_tri(w.tri_fast, __float_as_int(rec.y)), ray, 0.001f, te, t);
+                } else {  // wrapped leaves, boxes, volumes
+                    hit = leaf_t<false, true>(w, S, leaf, ray, 0.001f, te, rng, t, st);
+                }
+                if (hit) {
+                    te = t;
+                    found = leaf;
+                }
+                if (sp == 0) live = false;
+                else node = stack[(--sp) * RTW_AOV_BLOCK];
+            }
+            if (live && node >= 0) {
+                const float4 nb = w.node_b[node];
+                if (node_pass(w.node_a[node], nb, w.node_km[node], ray, rp, 0.001f, te)) {
+                    const int32_t lbits = __float_as_int(nb.z);
+                    const int32_t left = lbits >> 2, right = __float_as_int(nb.w);
+                    const bool fwd = ((sgn >> (lbits & 3)) & 1u) != 0u;  // ray.d[axis] > 0: left is the near child
+                    stack[(sp++) * RTW_AOV_BLOCK] = fwd ? right : left;
+                    node = fwd ? left : right;
+                } else if (sp == 0) {
+                    live = false;
+                } else {
+                    node = stack[(--sp) * RTW_AOV_BLOCK];
+                }
+            }
+        }
+        V3 a = v3(1.0f, 1.0f, 1.0f), nv;
+        if (found >= 0) {
+            Hit h;
+            leaf_record(w, found, ray, te, h, S);
+            nv = mul(add(h.n, v3(1.0f, 1.0f, 1.0f)), 0.5f);  // rendering.rs:110-113
+            dsum = dsum + te;
+            hits += 1u;
+            if (A.albedo) {
+                const int4 M = w.materials[h.material];
+                if ((M.x & (RTW_DMAT_IMAGE - 1)) != RTW_MAT_DIELECTRIC) {
+                    const V3 tc = (M.x & RTW_DMAT_IMAGE) != 0
+                                      ? image_texel<false>(w, M.z, (int32_t)((uint32_t)M.w >> 16), M.w & 0xFFFF, h, st)
+                                      : texture_sample<false, TX_ANY>(w, M.y, h, st, S);
+                    // the radiance of the emissive twin: 0 + 1 * texture (rendering.rs:62 on a DiffuseLight)
+                    a = add(v3(0.0f, 0.0f, 0.0f), conv(v3(1.0f, 1.0f, 1.0f), tc));
+                }
+            }
+        } else {
+            // RTW_MODE_NORMALS on a miss: the primary ray's background, through shade()'s expression
+            nv = add(v3(0.0f, 0.0f, 0.0f), conv(v3(1.0f, 1.0f, 1.0f), background(w.wc->bg, dot(v3(0.0f, 1.0f, 0.0f), ray.d))));
+        }
+        alb = add(alb, a);
+        nrm = add(nrm, nv);
+    }
+    A.hits[slot] = hits;
+    if (A.albedo) {
+        A.albedo[slot] = alb.x;
+        A.albedo[n + slot] = alb.y;
+        A.albedo[2 * n + slot] = alb.z;
+    }
+    if (A.normal) {
+        A.normal[slot] = nrm.x;
+        A.normal[n + slot] = nrm.y;
+        A.normal[2 * n + slot] = nrm.z;
+    }
+    if (A.depth) A.depth[slot] = dsum;
+}
+// what 0: three planes / (float)samples -> W*H*3; 1: depth_sum / (float)hits, 0 where nothing hit -> W*H;
+// 2: the hit counts -> W*H uint32_t.  One lane per pixel of the image.
+__global__ void aov_resolve_kernel(const float* __restrict__ planes, const uint32_t* __restrict__ hits, int32_t width,
+                                   int32_t height, int32_t tiles_x, uint32_t slots, uint32_t samples, int what, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)width * (uint32_t)height) return;
+    const uint32_t py = i / (uint32_t)width, px = i - py * (uint32_t)width;
+    const uint32_t slot = (((py >> 3) * (uint32_t)tiles_x + (px >> 3)) << 6) | ((py & 7u) << 3) | (px & 7u);
+    if (what == 0) {
+        const V3 r = divs(v3(planes[slot], planes[(size_t)slots + slot], planes[2 * (size_t)slots + slot]), (float)samples);
+        out[3 * (size_t)i] = r.x;
+        out[3 * (size_t)i + 1] = r.y;
+        out[3 * (size_t)i + 2] = r.z;
+    } else if (what == 1) {
+        const uint32_t h = hits[slot];
+        out[i] = h ? planes[slot] / (float)h : 0.0f;
+    } else {
+        ((uint32_t*)out)[i] = hits[slot];
+    }
+}
+
 __global__ void eval_scalar_kernel(int fn, const float* a, const float* b, int64_t n, float* out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -3915,6 +4117,7 @@ struct rtw_gpu_world {
     double last_mean = 0.0;
     uint64_t fingerprint = 0;  // rtw_world_fingerprint of the uploaded world (accumulator checkpoints)
     std::vector<struct rtw_accum*> accums;  // live accumulators: rtw_world_release orphans them (accum_orphan)
+    std::vector<struct rtw_aov*> aovs;      // live AOV accumulators, likewise (aov_orphan)
 };
 
 // experiment builds (-DRTW_WAVE_TIMING): per-wave start / end / queue-empty wall clocks (100 MHz) of
@@ -4483,11 +4686,13 @@ extern "C" RTW_API int rtw_primary_lists_host(const rtw_world* w, const rtw_rend
 }
 
 static void accum_orphan(struct rtw_accum* a);
+static void aov_orphan(struct rtw_aov* a);
 
 extern "C" RTW_API int rtw_world_release(rtw_gpu_world* g) {
     if (!g) return RTW_OK;
     (void)hipSetDevice(g->device);
     for (struct rtw_accum* a : g->accums) accum_orphan(a);
+    for (struct rtw_aov* a : g->aovs) aov_orphan(a);
     if (g->arena) (void)hipFree(g->arena);
     if (g->queue) (void)hipFree(g->queue);
     if (g->colors) (void)hipFree(g->colors);
@@ -5545,6 +5750,212 @@ extern "C" RTW_API int rtw_debug_compact(int device, const uint32_t* order, cons
     (void)hipFree(d);
     if (e != hipSuccess) return rtw::fail(RTW_ERR_HIP, std::string("rtw_debug_compact: ") + hipGetErrorString(e));
     return RTW_OK;
+}
+
+// ---- first-hit AOVs (rtw.h) -------------------------------------------------------
+struct rtw_aov {
+    rtw_gpu_world* g = nullptr;
+    rtw_aov_info info{};
+    int32_t tiles_x = 0;
+    uint32_t slots = 0;  // tiles * 64
+    float* planes = nullptr;  // one allocation: [albedo 3][normal 3][depth 1] planes of `slots` floats, as held
+    float* albedo = nullptr;
+    float* normal = nullptr;
+    float* depth = nullptr;
+    uint32_t* hits = nullptr;
+    // the accumulator's own leaf lists (the world's belong to its frames, whose shape may change under a running
+    // add): tiles counts, then tiles x pl_cap leaf indices; null: every tile walks
+    int32_t* pl_buf = nullptr;
+    int32_t pl_cap = 0, pl_tiles = 0;
+};
+
+// (rtw_world_release: as accum_orphan)
+static void aov_orphan(rtw_aov* a) {
+    if (a->planes) (void)hipFree(a->planes);
+    if (a->hits) (void)hipFree(a->hits);
+    if (a->pl_buf) (void)hipFree(a->pl_buf);
+    a->pl_buf = nullptr;
+    a->planes = a->albedo = a->normal = a->depth = nullptr;
+    a->hits = nullptr;
+    a->g = nullptr;
+}
+
+extern "C" RTW_API int rtw_aov_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t channels, rtw_aov** out) {
+    if (!p || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    // (the params first, the world last: the refusals below need no device)
+    if (p->layout == RTW_LAYOUT_TILES)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.layout: an AOV accumulator covers the whole image in RTW_LAYOUT_IMAGE");
+    if (p->layout != RTW_LAYOUT_IMAGE) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_render_params.layout is unknown");
+    if (p->part_count > 1)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.part_count: an AOV accumulator covers the whole image");
+    if (p->thread_count > 1)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.thread_count: AOV accumulators take 0 or 1 (no sample planes)");
+    if (channels == 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channels is 0: name at least one RTW_AOV_* channel");
+    if (channels & ~(RTW_AOV_ALBEDO | RTW_AOV_NORMAL | RTW_AOV_DEPTH))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channels holds an unknown bit");
+    if (p->reserved0 != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_render_params.reserved0 must be 0");
+    if (p->width < 2 || p->height < 2)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_render_params.width and height must be >= 2");
+    const int64_t tiles_x = ((int64_t)p->width + 7) / 8, tiles_y = ((int64_t)p->height + 7) / 8;
+    // (pixel indices and slots are 32-bit in the kernels, and the stream's pixel key is)
+    if (tiles_x * tiles_y * 64 >= (int64_t)0x7FFFFFFF)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.width x height: image too large");
+    if (!g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null world");
+    auto* a = new rtw_aov;
+    a->g = g;
+    a->tiles_x = (int32_t)tiles_x;
+    a->slots = (uint32_t)(tiles_x * tiles_y * 64);
+    rtw_aov_info& I = a->info;
+    I.version = 1;
+    I.channels = channels;
+    I.width = p->width;
+    I.height = p->height;
+    I.samples = 0;
+    I.reserved = 0;
+    I.seed = p->seed;
+    I.world_fingerprint = g->fingerprint;
+    (void)hipSetDevice(g->device);
+    const size_t n_planes = ((channels & RTW_AOV_ALBEDO) ? 3 : 0) + ((channels & RTW_AOV_NORMAL) ? 3 : 0) +
+                            ((channels & RTW_AOV_DEPTH) ? 1 : 0);
+    const size_t plane_bytes = (size_t)a->slots * sizeof(float);
+    hipError_t e = hipMalloc(&a->planes, n_planes * plane_bytes);
+    if (e == hipSuccess) e = hipMalloc(&a->hits, plane_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        aov_orphan(a);
+        delete a;
+        return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    float* next = a->planes;
+    if (channels & RTW_AOV_ALBEDO) a->albedo = next, next += 3 * (size_t)a->slots;
+    if (channels & RTW_AOV_NORMAL) a->normal = next, next += 3 * (size_t)a->slots;
+    if (channels & RTW_AOV_DEPTH) a->depth = next;
+    // (synchronous: the zeros are there before any stream's first add)
+    e = hipMemset(a->planes, 0, n_planes * plane_bytes);
+    if (e == hipSuccess) e = hipMemset(a->hits, 0, plane_bytes);
+    // The camera rays' leaf lists, where the megakernel would use them (ensure_primary_lists): a world of plain
+    // cullable spheres whose SAH tables hold the leaves' proof boxes, rays that admit the exact fast division.
+    // RTW_PRIMARY_LISTS=0 switches them off here too, RTW_PRIMARY_LIST_CAP sets the longest list.
+    const char* pl_env = std::getenv("RTW_PRIMARY_LISTS");
+    if (e == hipSuccess && g->pl_scope && g->mk_world && g->sah_nodes > 0 && g->leaf_count >= 1 &&
+        (pl_env ? pl_env[0] == '1' : RTW_PL_DEFAULT != 0)) {
+        const int32_t cap = (int32_t)std::min<size_t>((size_t)g->leaf_count, env_size("RTW_PRIMARY_LIST_CAP", RTW_BEAM_CAP_DEFAULT));
+        const size_t n = (size_t)(tiles_x * tiles_y);
+        e = hipMalloc(&a->pl_buf, n * (size_t)(1 + cap) * sizeof(int32_t));
+        std::vector<int32_t> cnt(n);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(primary_lists_kernel, dim3((unsigned)n), dim3(RTW_PL_GROUP), 0, nullptr, &g->w.wc->cam,
+                               g->w.leaf_fast, g->leaf_count, p->width, p->height, 8, 8, (int32_t)tiles_x, (int32_t)n, cap,
+                               a->pl_buf, a->pl_buf + n);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(cnt.data(), a->pl_buf, n * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) {
+            a->pl_cap = cap;
+            a->pl_tiles = (int32_t)n;
+            bool any = false;
+            for (int32_t c : cnt) any = any || c >= 0;
+            if (!any) {  // every tile walks
+                (void)hipFree(a->pl_buf);
+                a->pl_buf = nullptr;
+            }
+        }
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        aov_orphan(a);
+        delete a;
+        return rtw::fail(RTW_ERR_HIP, std::string("rtw_aov_create: ") + hipGetErrorString(e));
+    }
+    g->aovs.push_back(a);
+    *out = a;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_aov_release(rtw_aov* a) {
+    if (!a) return RTW_OK;
+    if (rtw_gpu_world* g = a->g) {  // (else rtw_world_release freed the device state)
+        (void)hipSetDevice(g->device);
+        g->aovs.erase(std::remove(g->aovs.begin(), g->aovs.end(), a), g->aovs.end());
+        aov_orphan(a);  // (hipFree waits for the launches that still use it)
+    }
+    delete a;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_aov_get_info(rtw_aov* a, rtw_aov_info* out) {
+    if (!a || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    *out = a->info;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_aov_add(rtw_aov* a, uint32_t n, void* stream) {
+    if (!a) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    if (n == 0) return RTW_OK;
+    if ((uint64_t)a->info.samples + n > 0xFFFFFFFFull)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's sample count would pass 32 bits");
+    const rtw_gpu_world* g = a->g;
+    HIP_TRY(hipSetDevice(g->device));
+    AovArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.w = g->w;
+    A.width = a->info.width;
+    A.height = a->info.height;
+    A.tiles_x = a->tiles_x;
+    A.slots = a->slots;
+    A.s_begin = a->info.samples;
+    A.n = n;
+    A.mk_world = g->mk_world;
+    A.seed_key = rtw_seed_key(a->info.seed);
+    A.sx = 1.0f / (float)(A.width - 1);  // as make_args
+    A.sy = 1.0f / (float)(A.height - 1);
+    A.ux = rtw_uniform_new(0.0f, 1.0f / (float)(A.width - 1));
+    A.uy = rtw_uniform_new(0.0f, 1.0f / (float)(A.height - 1));
+    A.albedo = a->albedo;
+    A.normal = a->normal;
+    A.depth = a->depth;
+    A.hits = a->hits;
+    A.pl_count = a->pl_buf;
+    A.pl_list = a->pl_buf ? a->pl_buf + (size_t)a->pl_tiles : nullptr;
+    A.pl_cap = a->pl_cap;
+    // the stack: one int32_t per level of the reference tree and lane (g->depth >= that tree's depth, <= RTW_STACK)
+    const size_t lds = (size_t)std::max(1, g->depth) * RTW_AOV_BLOCK * sizeof(int32_t);
+    const dim3 grid((a->slots + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK);
+    if (A.pl_count) hipLaunchKernelGGL(aov_kernel<true>, grid, dim3(RTW_AOV_BLOCK), lds, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(aov_kernel<false>, grid, dim3(RTW_AOV_BLOCK), lds, (hipStream_t)stream, A);
+    HIP_TRY(hipGetLastError());
+    a->info.samples += n;
+    return RTW_OK;
+}
+
+namespace {
+int aov_resolve(rtw_aov* a, int what, const float* planes, void* d_out, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(a->g->device));
+    const uint32_t pixels = (uint32_t)a->info.width * (uint32_t)a->info.height;
+    hipLaunchKernelGGL(aov_resolve_kernel, dim3((pixels + 255) / 256), dim3(256), 0, stream, planes, (const uint32_t*)a->hits,
+                       a->info.width, a->info.height, a->tiles_x, a->slots, a->info.samples, what, (float*)d_out);
+    HIP_TRY(hipGetLastError());
+    return RTW_OK;
+}
+}  // namespace
+
+extern "C" RTW_API int rtw_aov_resolve(rtw_aov* a, uint32_t channel, float* d_out, void* stream) {
+    if (!a || !d_out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    if (channel != RTW_AOV_ALBEDO && channel != RTW_AOV_NORMAL && channel != RTW_AOV_DEPTH)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channel is not one of RTW_AOV_ALBEDO, RTW_AOV_NORMAL, RTW_AOV_DEPTH");
+    if (!(a->info.channels & channel)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channel: the AOV accumulator does not hold it");
+    if (a->info.samples < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "resolve needs samples >= 1");
+    const float* planes = channel == RTW_AOV_ALBEDO ? a->albedo : channel == RTW_AOV_NORMAL ? a->normal : a->depth;
+    return aov_resolve(a, channel == RTW_AOV_DEPTH ? 1 : 0, planes, d_out, (hipStream_t)stream);
+}
+
+extern "C" RTW_API int rtw_aov_hits(rtw_aov* a, uint32_t* d_out, void* stream) {
+    if (!a || !d_out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    return aov_resolve(a, 2, nullptr, d_out, (hipStream_t)stream);
 }
 
 namespace {

@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _native as N
 from ._native import check, lib
+from .aov import AovAccumulator
 from .rendering import DEFAULT_SEED, DeviceWorld, RenderMode, Size2i, render_params
 from .world import World
 
@@ -228,13 +229,16 @@ class Accumulator:
         check(fn(self._h, C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return out
 
-    def denoised(self, guide=None, **options):
+    def denoised(self, guide=None, albedo=None, **options):
         """A denoised preview of the image so far: (W*H, 3) f32 on the host (with variance=True also the (W*H,)
         variance of each filtered pixel).  Resolves the image and `stderr()` on the device and runs a cached
         `Denoiser` on them (denoise.py; options: iterations, sigma_l, sigma_g, variance).  `guide` is an
         array or device tensor of shape (W*H, 1..4), or another Accumulator of this size and device whose image
-        is taken -- one in `RenderMode.Normals`, say.  Needs moments=True and samples >= 2.  Non-destructive: the
-        sums are only read, `image()` stays the exact image and further adds continue the frame.
+        is taken -- one in `RenderMode.Normals`, say -- or an `AovAccumulator`, whose normal image is taken.
+        `albedo` is an array or device tensor of shape (W*H, 3) or an `AovAccumulator`, whose albedo image is
+        taken: the filter then runs on the demodulated image (`Denoiser.run`).  An AOV accumulator of another size
+        or device, or one without samples, raises ValueError.  Needs moments=True and samples >= 2.
+        Non-destructive: the sums are only read, `image()` stays the exact image and further adds continue the frame.
 
         A filter needs the whole image: an accumulator with LAYOUT_TILES or part != (0, 1) raises ValueError.
         Rank users gather the image and the standard error and call `Denoiser.run` on rank 0."""
@@ -252,7 +256,21 @@ class Accumulator:
         if self.samples < 2:
             raise ValueError("denoised() needs samples >= 2")
         dev = torch.device("cuda", self.device)
-        if isinstance(guide, Accumulator):
+
+        def aov_image(name: str, aov: AovAccumulator, channel: str):
+            if (aov.size.width, aov.size.height) != (self.size.width, self.size.height) or aov.device != self.device:
+                raise ValueError(f"the {name} AOV accumulator has another size or device")
+            if aov.samples < 1:
+                raise ValueError(f"the {name} AOV accumulator holds no samples")
+            return aov.normal_device() if channel == "normal" else aov.albedo_device()
+
+        if isinstance(albedo, AovAccumulator):
+            albedo = aov_image("albedo", albedo, "albedo")
+        elif albedo is not None and not hasattr(albedo, "data_ptr"):
+            albedo = torch.from_numpy(np.ascontiguousarray(albedo, np.float32)).to(dev)
+        if isinstance(guide, AovAccumulator):
+            guide = aov_image("guide", guide, "normal")
+        elif isinstance(guide, Accumulator):
             if (guide.size.width, guide.size.height) != (self.size.width, self.size.height) or guide.device != self.device:
                 raise ValueError("the guide accumulator has another size or device")
             if guide.params.layout != N.LAYOUT_IMAGE or (guide.params.part_index, max(1, guide.params.part_count)) != (0, 1):
@@ -264,7 +282,7 @@ class Accumulator:
             self._denoiser = Denoiser(self.size, self.device)
         color = self._resolved_device(lib().rtw_accum_resolve)
         se = self._resolved_device(lib().rtw_accum_resolve_stderr)
-        res = self._denoiser.run_device(color, se, guide, color, **options)
+        res = self._denoiser.run_device(color, se, guide, color, albedo=albedo, **options)
         torch.cuda.current_stream(dev).synchronize()
         if isinstance(res, tuple):
             return res[0].cpu().numpy(), res[1].cpu().numpy()

@@ -1,0 +1,156 @@
+"""References for the first-hit AOVs (rtw_aov_*), all from the oracle as it is:
+
+* `Twin`: the emissive twin of a world -- a copy of `World.raw` with its own material and texture arrays, every
+  material a DIFFUSE_LIGHT of its own texture, a dielectric one of an appended solid white texture, no light rect,
+  background solid white.  At max_depth 2 the oracle's radiance of it is 0 + 1 * texture(first hit), 1 on a miss:
+  the albedo AOV.
+* `depth_hits`: the per-sample oracle loop (the (seed, pixel, sample) stream, the jitter, rtw_oracle_camera_ray,
+  rtw_oracle_scene_hit with the stream carried on) summing t in sample order.
+* `denoise_albedo`: tests/denoise_ref.denoise between the demodulation's pre-step and post-step, numpy f32.
+"""
+import ctypes as C
+
+import numpy as np
+
+import raytracinginaweekend_amd as R
+from oracle import pyoracle as O
+from oracle import pyref
+from raytracinginaweekend_amd import _native as N
+from tests import denoise_ref as D
+
+f32 = np.float32
+M64 = (1 << 64) - 1
+
+GPU_WORLDS = ["final_scene1", "final_scene2", "cornell_box", "cornell_box_smoke", "cornell_cube", "suzanne",
+              "earth_mapped", "earth_motion", "perlin_spheres", "moving_spheres", "defocus_blur"]
+
+
+class Twin:
+    """The emissive twin of `world`; quacks like a World for oracle/pyoracle.py (`ptr()`, `raw`)."""
+
+    def __init__(self, world):
+        self.world = world  # (the twin's other tables are the world's own)
+        src = world.raw
+        self.raw = N.World()
+        C.memmove(C.byref(self.raw), C.byref(src), C.sizeof(N.World))
+        nt, nm = src.texture_count, src.material_count
+        self.textures = (N.Texture * (nt + 1))()
+        if nt:
+            C.memmove(self.textures, src.textures, nt * C.sizeof(N.Texture))
+        white = self.textures[nt]
+        white.kind = N.TEX_SOLID
+        white.color[0] = white.color[1] = white.color[2] = 1.0
+        white.even = white.odd = white.perlin = white.image = -1
+        self.materials = (N.Material * max(1, nm))()
+        for i in range(nm):
+            m = src.materials[i]
+            self.materials[i].kind = N.MAT_DIFFUSE_LIGHT
+            self.materials[i].texture = nt if m.kind == N.MAT_DIELECTRIC else m.texture
+        self.raw.textures = C.cast(self.textures, C.POINTER(N.Texture))
+        self.raw.texture_count = nt + 1
+        self.raw.materials = C.cast(self.materials, C.POINTER(N.Material))
+        self.raw.has_light = 0
+        self.raw.background.kind = N.BG_SOLID
+        self.raw.background.color[0] = self.raw.background.color[1] = self.raw.background.color[2] = 1.0
+
+    def ptr(self):
+        return C.byref(self.raw)
+
+
+def twin_albedo(world, size, spp, seed):
+    """The albedo AOV of the oracle: the twin's frame at max_depth 2."""
+    return O.render(Twin(world), R.render_params(size, spp, 2, seed=seed))
+
+
+def mix64(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def sample_stream(seed, pixel, sample):
+    """rtw_sample_stream(rtw_seed_key(seed), pixel, sample) (include/rtw_scalar.h)."""
+    key = mix64((seed ^ 0x5EED5EED5EED5EED) & M64)
+    x = mix64(((pixel << 32) | sample) ^ key)
+    s1 = ((x ^ (x >> 32)) * 0xD6E8FEB86659FD93) & M64
+    return (1, s1) if (x | s1) == 0 else (x, s1)
+
+
+def uniform_new(low, high):
+    """rtw_uniform_new: (low, scale), the scale shrunk until scale * max_rand + low < high."""
+    low, high = f32(low), f32(high)
+    max_rand = np.uint32((0xFFFFFFFF >> 9) | 0x3F800000).view(f32) - f32(1)
+    scale = high - low
+    while scale * max_rand + low >= high:
+        scale = (scale.view(np.uint32) - np.uint32(1)).view(f32)
+    return low, scale
+
+
+def primary_hit(world, size, seed, x, y, s):
+    """The oracle's first hit of sample `s` of pixel (x, y): an OracleHit (hit == 0: a miss)."""
+    W, H = size.width, size.height
+    L = O.lib()
+    (lx, sx), (ly, sy) = uniform_new(0, f32(1) / f32(W - 1)), uniform_new(0, f32(1) / f32(H - 1))
+    rng = pyref.Xoro(*sample_stream(seed, y * W + x, s))
+    jx = rng._value0_1() * sx + lx
+    jy = rng._value0_1() * sy + ly
+    px = f32(x) * (f32(1) / f32(W - 1)) + jx
+    py = f32(y) * (f32(1) / f32(H - 1)) + jy
+    state = (C.c_uint64 * 2)(rng.s0, rng.s1)
+    o, d, t = (C.c_float * 3)(), (C.c_float * 3)(), C.c_float()
+    assert L.rtw_oracle_camera_ray(C.byref(world.raw.camera), px, py, state, o, d, C.byref(t)) == 0
+    h = O.OracleHit()
+    assert L.rtw_oracle_scene_hit(world.ptr(), o, d, t, f32(0.001), f32(np.inf), state, C.byref(h)) == 0
+    return h
+
+
+def depth_hits(world, size, spp, seed):
+    """(depth (W*H,) f32, hits (W*H,) uint32): depth_sum = depth_sum + t over the samples that hit, in sample
+    order from +0; depth = hits ? depth_sum / (float)hits : 0."""
+    W, H = size.width, size.height
+    depth = np.zeros(W * H, f32)
+    hits = np.zeros(W * H, np.uint32)
+    for pix in range(W * H):
+        total = f32(0)
+        for s in range(spp):
+            h = primary_hit(world, size, seed, pix % W, pix // W, s)
+            if h.hit:
+                total = total + f32(h.t)
+                hits[pix] += 1
+        if hits[pix]:
+            depth[pix] = total / f32(hits[pix])
+    return depth, hits
+
+
+def denoise_albedo(color, se, guide, albedo, size, iterations=3, sigma_l=1.5, sigma_g=0.35):
+    """include/rtw_denoise.h's albedo demodulation around tests/denoise_ref.denoise.  Returns ((W*H, 3), (W*H,))."""
+    color, se, albedo = (np.asarray(a, f32).reshape(-1, 3) for a in (color, se, albedo))
+    with np.errstate(all="ignore"):
+        Dv = np.where(albedo >= f32(1 / 64), albedo, f32(1 / 64))
+        c1, e1 = color / Dv, se / Dv
+        assert c1.dtype == np.float32 and e1.dtype == np.float32
+        a_ok = D.finite(albedo).all(axis=1)
+        # a pixel with a non-finite albedo channel is left out: a NaN colour does that in denoise()
+        filtered, var = D.denoise(np.where(a_ok[:, None], c1, D.NAN), e1, guide, size, iterations, sigma_l, sigma_g)
+        l = (c1[:, 0] + c1[:, 1]) + c1[:, 2]
+        v = e1 * e1
+        ok = a_ok & D.finite(l) & D.finite((v[:, 0] + v[:, 1]) + v[:, 2])
+        if guide is not None and np.asarray(guide).size:
+            ok = ok & D.finite(np.asarray(guide).reshape(len(ok), -1)).all(axis=1)
+        out = np.where(ok[:, None], filtered * Dv, color)
+    assert out.dtype == np.float32
+    return out, var
+
+
+def synthetic_albedo(size, seed):
+    """An albedo image for denoise_ref.synthetic's cases: ordinary values in [0.05, 1), and among them values below
+    1/64, 0, a negative one, NaN, +inf and 15 (a lamp), one channel of a pixel each."""
+    n = size[0] * size[1]
+    rng = np.random.default_rng(seed + 12345)
+    a = (f32(0.05) + f32(0.95) * rng.random((n, 3), dtype=f32)).astype(f32)
+    special = [f32(0.01), f32(0), f32(np.nan), f32(np.inf), f32(15), f32(-0.5), f32(1 / 64)]
+    where = rng.permutation(n)
+    for j, v in enumerate(special):
+        for i in where[j::len(special)][:max(1, n // 30)] if n >= len(special) else where[j % n:j % n + 1]:
+            a[i, j % 3] = v
+    return a
