@@ -344,7 +344,9 @@ RTW_API int rtw_render_device(rtw_gpu_world* gw, const rtw_render_params* params
  * on worlds whose kernel keeps the generic leaf tables in LDS (wrapped, box or volume leaves: the
  * "true" in the fifth place of rtw_world_kernel_name), which add single samples.  One with
  * RTW_ACCUM_MOMENTS always takes single-sample items, its squares being summed in the accumulate
- * pass.  rtw_world_last_frame reports an add like a frame.  DESIGN.md 5.5c.
+ * pass; so does one with RTW_ACCUM_FINITE, whose filter sees the samples one by one in that pass (a
+ * whole-pixel launch sums inside the render kernel and cannot filter).  rtw_world_last_frame reports an
+ * add like a frame.  DESIGN.md 5.5c.
  *
  * Adaptive sampling (RTW_ACCUM_ADAPTIVE, needs RTW_ACCUM_MOMENTS).  The accumulator also
  * keeps one uint32_t tile_stop per local tile (the partition's tiles in slot order): 0 = the tile is
@@ -356,10 +358,25 @@ RTW_API int rtw_render_device(rtw_gpu_world* gw, const rtw_render_params* params
  * n holds, bit for bit, the pixels of a frame at samples_per_pixel = n (and of the reference at that
  * spp); the stop decision is a fixed f32 expression of the sums and squares (include/rtw_adapt.h), so a
  * host can replay the whole run; the stop map is part of the output.  Like every accumulator with
- * moments, an adaptive one takes single-sample work items. */
+ * moments, an adaptive one takes single-sample work items.
+ *
+ * Finite-sample accumulation (RTW_ACCUM_FINITE; include/rtw_finite.h has the definition).  The
+ * reference's 0/0 pdf quirk makes an occasional whole sample NaN, and one NaN sample turns its pixel's sum NaN for
+ * good.  With this flag the accumulate pass leaves out every sample with a channel that is NaN or +-inf: it adds
+ * nothing to the sums (and squares) and is not counted.  The accumulator also keeps one uint32_t `kept` per slot,
+ * the samples that entered the sums; rejected = the slot's sample count - kept.  The resolves, the noise estimate
+ * and rtw_accum_adapt divide by the pixel's own kept in place of the sample count (kept == 0 resolves to +0.0;
+ * kept < 2 has no finite standard error and is left out of the noise mean and of a tile's E, as every pixel with
+ * a non-finite value is).  The counts are part of the output, as the stop map is.  The flag combines with
+ * RTW_ACCUM_MOMENTS and RTW_ACCUM_ADAPTIVE and works without either; it changes nothing for accumulators created
+ * without it, nor for rtw_render*.  A finite accumulator always takes single-sample work items, as one with
+ * moments does: the accumulate pass is where samples are seen one by one, so a whole-pixel launch cannot filter.
+ * On a pixel with no rejected sample every output is the plain accumulator's, bit for bit.  Dropping samples
+ * biases the estimate (the dropped paths carried energy): the exact reference image stays the plain accumulator's. */
 typedef struct rtw_accum rtw_accum;
 #define RTW_ACCUM_MOMENTS 1u  /* also keep per-channel sums of squares (the noise estimate) */
 #define RTW_ACCUM_ADAPTIVE 2u /* per-tile stop map: converged tiles take no more samples */
+#define RTW_ACCUM_FINITE 4u   /* leave non-finite samples out of the sums; per-slot kept counts */
 typedef struct rtw_accum_info { /* all fields fixed-width, no padding; also the checkpoint header */
     uint32_t version; /* 1 */
     uint32_t flags;   /* RTW_ACCUM_* */
@@ -438,6 +455,19 @@ RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const flo
 RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_tile_stop);
 RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                       const float* host_squares, const uint32_t* host_tile_stop);
+/* RTW_ACCUM_FINITE only (else RTW_ERR_INVALID_ARGUMENT): the kept count of each pixel or slot, laid out and padded
+ * as rtw_accum_resolve_samples lays out the sample counts.  Asynchronous. */
+RTW_API int rtw_accum_resolve_kept(rtw_accum* a, uint32_t* d_out, void* stream);
+/* One export / import pair for every flag combination: sums always; squares with RTW_ACCUM_MOMENTS, tile_stop
+ * with RTW_ACCUM_ADAPTIVE, kept (one uint32_t per slot) with RTW_ACCUM_FINITE.  A pointer the accumulator's flags
+ * call for must be non-null and any other must be NULL, else RTW_ERR_INVALID_ARGUMENT.  The import checks `info`
+ * and tile_stop as the older pairs do, and refuses a kept[slot] above the slot's sample count, or non-zero in a
+ * padding slot, with a message naming kept.  The two older pairs refuse an accumulator with RTW_ACCUM_FINITE by
+ * name (its state includes kept) and are otherwise unchanged.  Synchronous. */
+RTW_API int rtw_accum_export_state(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_tile_stop,
+                                   uint32_t* host_kept);
+RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                   const float* host_squares, const uint32_t* host_tile_stop, const uint32_t* host_kept);
 
 /* ---- first-hit AOVs ------------------------------------------------------------------------- */
 /* An AOV accumulator keeps, per pixel of the whole image, running sums of what the camera rays hit first:

@@ -12,6 +12,7 @@ from .progressive import (
     Accumulator,
     AccumState,
     render_adaptive,
+    render_finite,
     render_progressive,
     render_to_noise,
     world_fingerprint,
@@ -66,6 +67,7 @@ __all__ = [
     "render_aov",
     "render_devices",
     "render_adaptive",
+    "render_finite",
     "render_params",
     "render_progressive",
     "render_to_noise",

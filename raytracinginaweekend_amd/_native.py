@@ -192,6 +192,7 @@ class RenderStats(C.Structure):
 
 ACCUM_MOMENTS = 1  # RTW_ACCUM_MOMENTS
 ACCUM_ADAPTIVE = 2  # RTW_ACCUM_ADAPTIVE
+ACCUM_FINITE = 4  # RTW_ACCUM_FINITE
 
 
 class AccumInfo(C.Structure):  # rtw_accum_info: fixed-width fields, no padding (also the checkpoint header)
@@ -328,6 +329,16 @@ _SIGS = {
     "rtw_accum_export_adaptive": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtw_accum_import_adaptive": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_uint32)]),
+    "rtw_accum_resolve_kept": (C.c_int, [_P, _P, _P]),
+    "rtw_accum_export_state": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32)]),
+    "rtw_accum_import_state": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rtw_finite_accumulate_host": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "rtw_adapt_tiles_finite_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                              C.POINTER(RenderParams), C.c_uint32, C.c_float, C.c_uint32,
+                                              C.POINTER(C.c_uint32)]),
     "rtw_aov_create": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.POINTER(_P)]),
     "rtw_aov_release": (C.c_int, [_P]),
     "rtw_aov_add": (C.c_int, [_P, C.c_uint32, _P]),

@@ -36,6 +36,7 @@
 #include "../../include/rtw_cull.h"
 #include "../../include/rtw_beam.h"
 #include "../../include/rtw_adapt.h"
+#include "../../include/rtw_finite.h"
 #include "rtw_common.h"
 
 #ifndef RTW_BLOCK
@@ -3019,6 +3020,43 @@ __global__ void accumulate_moments_kernel(const float* __restrict__ colors, uint
     Q[1] = sq.y;
     Q[2] = sq.z;
 }
+// An accumulator's add with RTW_ACCUM_FINITE (rtw_finite.h): accumulate_moments_kernel's pass, but a sample with a
+// NaN or infinite channel adds nothing and is not counted.  One slot per lane; sum, sq and kept stay in registers
+// over the launch's samples, so each array takes one read and one write per launch.  MOMENTS false: no squares
+// (the pointer is not read).  Stopped tiles are skipped as above.
+template <bool MOMENTS>
+__global__ void accumulate_finite_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G,
+                                         float* __restrict__ sums, float* __restrict__ squares,
+                                         uint32_t* __restrict__ kept, const uint32_t* __restrict__ tile_stop) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    if (!slot_pixel(G, slot, px, py)) return;
+    if (tile_stop && tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)] != 0) return;
+    float* S = sums + 3 * (size_t)slot;
+    float* Q = MOMENTS ? squares + 3 * (size_t)slot : nullptr;
+    V3 sum = v3(S[0], S[1], S[2]), sq = v3(0.0f, 0.0f, 0.0f);
+    if (MOMENTS) sq = v3(Q[0], Q[1], Q[2]);
+    uint32_t k = kept[slot];
+    const float* c = colors + 3 * (size_t)slot;
+    for (uint32_t s = 0; s < n_samples; ++s, c += 3 * (size_t)G.total) {
+        const V3 col = v3(c[0], c[1], c[2]);
+        // (a branch, not selects: the select form compiled to 52 B of scratch and ran the pass 4.5x slower,
+        // profiles/r12/pass_ab_select.txt)
+        if (!rtw_finite_sample(col.x, col.y, col.z)) continue;
+        sum = add(sum, col);
+        if (MOMENTS) sq = add(sq, conv(col, col));
+        ++k;
+    }
+    S[0] = sum.x;
+    S[1] = sum.y;
+    S[2] = sum.z;
+    if (MOMENTS) {
+        Q[0] = sq.x;
+        Q[1] = sq.y;
+        Q[2] = sq.z;
+    }
+    kept[slot] = k;
+}
 // the standard error of a channel's mean from its sum and sum of squares (rtw.h: the order is the contract;
 // the arithmetic is rtw_adapt.h's, shared with the host)
 __device__ __forceinline__ float accum_se(float sum, float sq, uint32_t samples, float& mean) {
@@ -3102,6 +3140,74 @@ __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const floa
         part_count[blockIdx.x] = sh_cnt[0];
     }
 }
+// The resolves of an accumulator with RTW_ACCUM_FINITE (kernels of their own: the ones above compile as before).
+// what 0: sum / kept, +0 for kept == 0; 1: the standard error with n = kept (not finite for kept < 2, rtw_finite.h);
+// 3: kept itself, laid out and padded as what == 2 above lays out the sample counts.
+__global__ void accum_resolve_finite_kernel(const float* __restrict__ sums, const float* __restrict__ squares,
+                                            const uint32_t* __restrict__ kept, SlotGeom G, int what, float* out,
+                                            int layout) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    const bool owned = slot_pixel(G, slot, px, py);
+    if (what == 3) {
+        uint32_t* o = (uint32_t*)out;
+        if (layout == RTW_LAYOUT_TILES) {
+            if (slot < G.total) o[slot] = owned ? kept[slot] : 0u;
+        } else if (owned) {
+            o[(size_t)py * G.width + px] = kept[slot];
+        }
+        return;
+    }
+    if (!owned) return;
+    const uint32_t n = kept[slot];
+    const float* S = sums + 3 * (size_t)slot;
+    V3 r;
+    if (what == 0) {
+        r = v3(rtw_finite_mean(S[0], n), rtw_finite_mean(S[1], n), rtw_finite_mean(S[2], n));
+    } else {
+        const float* Q = squares + 3 * (size_t)slot;
+        float m;
+        r = v3(accum_se(S[0], Q[0], n, m), accum_se(S[1], Q[1], n, m), accum_se(S[2], Q[2], n, m));
+    }
+    float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
+    o[0] = r.x;
+    o[1] = r.y;
+    o[2] = r.z;
+}
+// accum_noise_kernel with each pixel's own kept as its n (the same fixed tree order)
+__global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_finite_kernel(const float* __restrict__ sums,
+                                                                             const float* __restrict__ squares,
+                                                                             const uint32_t* __restrict__ kept, SlotGeom G,
+                                                                             double* __restrict__ part_sum,
+                                                                             uint32_t* __restrict__ part_count) {
+    __shared__ double sh_sum[RTW_NOISE_BLOCK];
+    __shared__ uint32_t sh_cnt[RTW_NOISE_BLOCK];
+    const uint32_t slot = blockIdx.x * RTW_NOISE_BLOCK + threadIdx.x;
+    double v = 0.0;
+    uint32_t n = 0;
+    int32_t px, py;
+    if (slot_pixel(G, slot, px, py)) {
+        const float e = rtw_adapt_pixel(sums + 3 * (size_t)slot, squares + 3 * (size_t)slot, kept[slot]);
+        if (rtw_adapt_finite(e)) {  // (false for NaN: every pixel with kept < 2)
+            v = (double)e;
+            n = 1;
+        }
+    }
+    sh_sum[threadIdx.x] = v;
+    sh_cnt[threadIdx.x] = n;
+    __syncthreads();
+    for (int step = RTW_NOISE_BLOCK / 2; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step) {
+            sh_sum[threadIdx.x] += sh_sum[threadIdx.x + step];
+            sh_cnt[threadIdx.x] += sh_cnt[threadIdx.x + step];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part_sum[blockIdx.x] = sh_sum[0];
+        part_count[blockIdx.x] = sh_cnt[0];
+    }
+}
 
 // ---- adaptive sampling (RTW_ACCUM_ADAPTIVE) ------------------------------------------
 // rtw_accum_adapt's tile test: one wave per local tile (RTW_ADAPT_BLOCK / 64 tiles per block; nothing depends
@@ -3126,6 +3232,36 @@ __global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_kernel(const floa
         if (!rtw_adapt_slot_pixel(&G, lt, it, &px, &py)) continue;
         const size_t at = 3 * ((size_t)lt * (size_t)per_tile + (size_t)it);
         E = rtw_adapt_max(E, rtw_adapt_pixel(sums + at, squares + at, samples));
+    }
+    for (int off = 32; off > 0; off >>= 1) {  // every lane's E is finite or -inf: the maximum has no order
+        const float o = __shfl_xor(E, off, 64);
+        E = o > E ? o : E;
+    }
+    if (lane == 0) {
+        const uint32_t stop = rtw_adapt_stop(rtw_adapt_tile_e(E), samples, target, min_samples);
+        if (stop) tile_stop[lt] = stop;
+    }
+}
+// adapt_tiles_kernel for an accumulator with RTW_ACCUM_FINITE: each pixel's e from its own kept (rtw_finite.h);
+// the stop rule still compares the frontier `samples` with min_samples.
+__global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_finite_kernel(const float* __restrict__ sums,
+                                                                             const float* __restrict__ squares,
+                                                                             const uint32_t* __restrict__ kept,
+                                                                             rtw_adapt_geom G, uint32_t samples,
+                                                                             float target, uint32_t min_samples,
+                                                                             uint32_t* __restrict__ tile_stop) {
+    const int32_t lane = (int32_t)(threadIdx.x & 63u);
+    const int64_t lt64 = (int64_t)blockIdx.x * (RTW_ADAPT_BLOCK / 64) + (int64_t)(threadIdx.x >> 6);
+    if (lt64 >= (int64_t)G.local_tiles) return;  // wave-uniform
+    const int32_t lt = (int32_t)lt64;
+    if (tile_stop[lt] != 0) return;  // wave-uniform: a stopped tile stays stopped
+    const int32_t per_tile = G.tile_w * G.tile_h;
+    float E = rtw_adapt_none();
+    for (int32_t it = lane; it < per_tile; it += 64) {
+        int32_t px, py;
+        if (!rtw_adapt_slot_pixel(&G, lt, it, &px, &py)) continue;
+        const size_t slot = (size_t)lt * (size_t)per_tile + (size_t)it;
+        E = rtw_adapt_max(E, rtw_adapt_pixel(sums + 3 * slot, squares + 3 * slot, kept[slot]));
     }
     for (int off = 32; off > 0; off >>= 1) {  // every lane's E is finite or -inf: the maximum has no order
         const float o = __shfl_xor(E, off, 64);
@@ -5095,6 +5231,7 @@ struct AccumRun {
     const uint32_t* tile_stop = nullptr;
     uint32_t* active_perm = nullptr;
     uint32_t active = 0;
+    uint32_t* kept = nullptr;  // RTW_ACCUM_FINITE: the per-slot kept counts (else null)
 };
 int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStream_t stream,
                       std::vector<uint64_t>* launch_items, const AccumRun* acc, bool acc_allow_wp = true);
@@ -5130,7 +5267,9 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
     // An accumulator that keeps moments always takes single-sample items: the squares are summed in the
     // accumulate pass, so the render kernel holds no extra registers for them
     // (... nor one whose world takes a GEN kernel: launch_render's RTW_ACC_NO_WP, render_frame)
-    if (!stats && A.thread_count <= 1 && !(acc && (acc->squares || !acc_allow_wp))) {
+    // ... nor one with RTW_ACCUM_FINITE: its filter sees the samples one by one in the accumulate pass, and a
+    // whole-pixel launch sums inside the render kernel
+    if (!stats && A.thread_count <= 1 && !(acc && (acc->squares || acc->kept || !acc_allow_wp))) {
         const uint64_t lanes = (uint64_t)std::max(1, g->cus) * RTW_BLOCK;
         const char* wp = std::getenv("RTW_WHOLE_PIXEL");
         if (wp && wp[0] == '1') A.whole_pixel = 1;
@@ -5268,6 +5407,14 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         const unsigned blocks = (A.total + 255) / 256;
         if (A.whole_pixel) {
             // the render kernel wrote the pixels
+        } else if (acc && acc->kept) {
+            const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
+            if (acc->squares)
+                hipLaunchKernelGGL(accumulate_finite_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
+                                   s1 - s0, G, acc->sums, acc->squares, acc->kept, acc->tile_stop);
+            else
+                hipLaunchKernelGGL(accumulate_finite_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
+                                   s1 - s0, G, acc->sums, (float*)nullptr, acc->kept, acc->tile_stop);
         } else if (acc && acc->squares) {
             const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
             hipLaunchKernelGGL(accumulate_moments_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
@@ -5343,6 +5490,7 @@ struct rtw_accum {
     rtw_accum_info info{};
     float* sums = nullptr;     // 3 floats per slot, owned; padding slots stay zero
     float* squares = nullptr;  // the same with RTW_ACCUM_MOMENTS, else null
+    uint32_t* kept = nullptr;  // RTW_ACCUM_FINITE: one count per slot (padding slots stay zero), else null
     double* noise_sum = nullptr;  // rtw_accum_noise: per-block partials (device), grown on first use
     uint32_t* noise_cnt = nullptr;
     // RTW_ACCUM_ADAPTIVE: the stop map, the compacted tile order of the adds (tiles + 1
@@ -5358,12 +5506,14 @@ struct rtw_accum {
 static void accum_orphan(rtw_accum* a) {
     if (a->sums) (void)hipFree(a->sums);
     if (a->squares) (void)hipFree(a->squares);
+    if (a->kept) (void)hipFree(a->kept);
     if (a->noise_sum) (void)hipFree(a->noise_sum);
     if (a->noise_cnt) (void)hipFree(a->noise_cnt);
     if (a->tile_stop) (void)hipFree(a->tile_stop);
     if (a->active_perm) (void)hipFree(a->active_perm);
     a->tile_stop = a->active_perm = nullptr;
     a->sums = a->squares = nullptr;
+    a->kept = nullptr;
     a->noise_sum = nullptr;
     a->noise_cnt = nullptr;
     a->g = nullptr;
@@ -5402,15 +5552,21 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs an accumulator with RTW_ACCUM_MOMENTS");
     if (what == 1 && a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs samples >= 2");
     // (what == 2, the sample counts: any accumulator at any point; a fresh one holds 0 everywhere)
+    if (what == 3 && !a->kept) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the kept counts need an accumulator with RTW_ACCUM_FINITE");
     KArgs A;
     int rc = accum_args(a, 1, A);
     if (rc != RTW_OK) return rc;
     if (A.total == 0) return RTW_OK;
     rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
-    hipLaunchKernelGGL(accum_resolve_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream, (const float*)a->sums,
-                       (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop, what, d_out,
-                       A.layout);
+    if (a->kept && what != 2)  // a finite accumulator divides by the pixel's own kept
+        hipLaunchKernelGGL(accum_resolve_finite_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream,
+                           (const float*)a->sums, (const float*)a->squares, (const uint32_t*)a->kept, accum_geom(A), what,
+                           d_out, A.layout);
+    else
+        hipLaunchKernelGGL(accum_resolve_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream, (const float*)a->sums,
+                           (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop, what,
+                           d_out, A.layout);
     HIP_TRY(hipGetLastError());
     return accum_leave(a, stream);
 }
@@ -5418,7 +5574,7 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
 
 extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t flags, rtw_accum** out) {
     if (!g || !p || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
-    if (flags & ~(RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown accumulator flags");
+    if (flags & ~(RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE | RTW_ACCUM_FINITE)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown accumulator flags");
     if ((flags & RTW_ACCUM_ADAPTIVE) && !(flags & RTW_ACCUM_MOMENTS))
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "RTW_ACCUM_ADAPTIVE needs RTW_ACCUM_MOMENTS (the stop test reads the squares)");
     if (p->thread_count > 1)
@@ -5456,6 +5612,8 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     const size_t bytes = std::max<size_t>(16, (size_t)A.total * 3 * sizeof(float));
     hipError_t e = hipMalloc(&a->sums, bytes);
     if (e == hipSuccess && (flags & RTW_ACCUM_MOMENTS)) e = hipMalloc(&a->squares, bytes);
+    const size_t kept_bytes = std::max<size_t>(16, (size_t)A.total * sizeof(uint32_t));
+    if (e == hipSuccess && (flags & RTW_ACCUM_FINITE)) e = hipMalloc(&a->kept, kept_bytes);
     a->tiles = a->active = A.total / (uint32_t)(A.tile_w * A.tile_h);
     const size_t stop_bytes = ((size_t)a->tiles + 1) * sizeof(uint32_t);
     if (flags & RTW_ACCUM_ADAPTIVE) {
@@ -5470,6 +5628,7 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     // (synchronous: the zeros are there before any stream's first add)
     e = hipMemset(a->sums, 0, bytes);
     if (e == hipSuccess && a->squares) e = hipMemset(a->squares, 0, bytes);
+    if (e == hipSuccess && a->kept) e = hipMemset(a->kept, 0, kept_bytes);
     if (e == hipSuccess && a->tile_stop) e = hipMemset(a->tile_stop, 0, stop_bytes);
     if (e == hipSuccess && a->active_perm) e = hipMemset(a->active_perm, 0, stop_bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -5511,6 +5670,7 @@ extern "C" RTW_API int rtw_accum_add(rtw_accum* a, uint32_t n, void* stream) {
     A.out = nullptr;  // an add writes the accumulator's state only
     HIP_TRY(hipSetDevice(a->g->device));
     AccumRun run{a->sums, a->squares, a->info.samples};
+    run.kept = a->kept;
     if (a->tile_stop && a->active < a->tiles) {  // (all active: exactly a plain moments accumulator's add)
         run.tile_stop = a->tile_stop;
         run.active_perm = a->active_perm;
@@ -5549,9 +5709,13 @@ extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* nois
         HIP_TRY(hipMalloc(&a->noise_sum, (size_t)blocks * sizeof(double)));
         HIP_TRY(hipMalloc(&a->noise_cnt, (size_t)blocks * sizeof(uint32_t)));
     }
-    hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, (const float*)a->sums,
-                       (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop, a->noise_sum,
-                       a->noise_cnt);
+    if (a->kept)
+        hipLaunchKernelGGL(accum_noise_finite_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, (const float*)a->sums,
+                           (const float*)a->squares, (const uint32_t*)a->kept, accum_geom(A), a->noise_sum, a->noise_cnt);
+    else
+        hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, (const float*)a->sums,
+                           (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop,
+                           a->noise_sum, a->noise_cnt);
     HIP_TRY(hipGetLastError());
     rc = accum_leave(a, stream);
     if (rc != RTW_OK) return rc;
@@ -5572,7 +5736,7 @@ extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* nois
 }
 
 namespace {
-int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop) {
+int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop, uint32_t* host_kept = nullptr) {
     if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
@@ -5583,11 +5747,38 @@ int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* 
     HIP_TRY(hipMemcpy(host_sums, a->sums, bytes, hipMemcpyDeviceToHost));
     if (a->squares) HIP_TRY(hipMemcpy(host_squares, a->squares, bytes, hipMemcpyDeviceToHost));
     if (host_stop) HIP_TRY(hipMemcpy(host_stop, a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (host_kept) HIP_TRY(hipMemcpy(host_kept, a->kept, (size_t)a->info.slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RTW_OK;
+}
+
+// the two older pairs on an accumulator with RTW_ACCUM_FINITE: its state includes kept
+int refuse_finite(const rtw_accum* a, const char* call) {
+    if (!a || !(a->info.flags & RTW_ACCUM_FINITE)) return RTW_OK;
+    return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(call) + ": the accumulator has RTW_ACCUM_FINITE, whose state includes "
+                                                   "kept: use rtw_accum_export_state / rtw_accum_import_state");
+}
+
+// rtw_accum_export_state / rtw_accum_import_state: a pointer the flags call for is non-null, any other is null
+int state_pointers(const rtw_accum* a, const void* squares, const void* stop, const void* kept) {
+    const struct {
+        uint32_t flag;
+        const void* p;
+        const char* name;
+        const char* flag_name;
+    } want[3] = {{RTW_ACCUM_MOMENTS, squares, "squares", "RTW_ACCUM_MOMENTS"},
+                 {RTW_ACCUM_ADAPTIVE, stop, "tile_stop", "RTW_ACCUM_ADAPTIVE"},
+                 {RTW_ACCUM_FINITE, kept, "kept", "RTW_ACCUM_FINITE"}};
+    for (const auto& w : want) {
+        const bool has = (a->info.flags & w.flag) != 0;
+        if (has && !w.p) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("null ") + w.name + " (the accumulator has " + w.flag_name + ")");
+        if (!has && w.p)
+            return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(w.name) + " given, but the accumulator has no " + w.flag_name);
+    }
     return RTW_OK;
 }
 
 int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums, const float* host_squares,
-                 const uint32_t* host_stop) {
+                 const uint32_t* host_stop, const uint32_t* host_kept = nullptr) {
     if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     const rtw_accum_info& M = a->info;
@@ -5623,6 +5814,28 @@ int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sum
             active += host_stop[t] == 0 ? 1u : 0u;
         }
     }
+    if (host_kept) {  // at most the slot's sample count; zero where no pixel is
+        rtw_adapt_geom G;
+        if (rtw_adapt_geom_of(&a->p, &G) != 0 || (uint32_t)G.local_tiles != a->tiles)
+            return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
+        const int32_t per_tile = G.tile_w * G.tile_h;
+        for (int32_t lt = 0; lt < G.local_tiles; ++lt) {
+            const uint32_t n = host_stop && host_stop[lt] ? host_stop[lt] : info->samples;
+            for (int32_t it = 0; it < per_tile; ++it) {
+                const size_t slot = (size_t)lt * (size_t)per_tile + (size_t)it;
+                int32_t px, py;
+                const uint32_t k = host_kept[slot];
+                if (!rtw_adapt_slot_pixel(&G, lt, it, &px, &py)) {
+                    if (k != 0)
+                        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "kept[" + std::to_string(slot) + "] = " + std::to_string(k) +
+                                                                       ": a padding slot holds 0");
+                } else if (k > n) {
+                    return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "kept[" + std::to_string(slot) + "] = " + std::to_string(k) +
+                                                                   " is above the slot's sample count (" + std::to_string(n) + ")");
+                }
+            }
+        }
+    }
     HIP_TRY(hipSetDevice(a->g->device));
     if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
     const size_t bytes = (size_t)M.slots * 3 * sizeof(float);
@@ -5630,6 +5843,7 @@ int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sum
         HIP_TRY(hipMemcpy(a->sums, host_sums, bytes, hipMemcpyHostToDevice));
         if (a->squares) HIP_TRY(hipMemcpy(a->squares, host_squares, bytes, hipMemcpyHostToDevice));
         if (host_stop) HIP_TRY(hipMemcpy(a->tile_stop, host_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (host_kept) HIP_TRY(hipMemcpy(a->kept, host_kept, (size_t)M.slots * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (host_stop) a->h_stop.assign(host_stop, host_stop + a->tiles);
     a->active = active;
@@ -5648,16 +5862,19 @@ int64_t tile_pixels(const rtw_accum_info& I, uint32_t lt) {
 }  // namespace
 
 extern "C" RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares) {
+    if (refuse_finite(a, "rtw_accum_export") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     return accum_export(a, host_sums, host_squares, nullptr);
 }
 
 extern "C" RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                         const float* host_squares) {
+    if (refuse_finite(a, "rtw_accum_import") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     return accum_import(a, info, host_sums, host_squares, nullptr);
 }
 
 extern "C" RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop) {
     if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (refuse_finite(a, "rtw_accum_export_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     if (a->g && !a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
     return accum_export(a, host_sums, host_squares, host_stop);
 }
@@ -5665,7 +5882,29 @@ extern "C" RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums,
 extern "C" RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                                  const float* host_squares, const uint32_t* host_stop) {
     if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (refuse_finite(a, "rtw_accum_import_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     return accum_import(a, info, host_sums, host_squares, host_stop);
+}
+
+extern "C" RTW_API int rtw_accum_export_state(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop,
+                                              uint32_t* host_kept) {
+    if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    const int rc = state_pointers(a, host_squares, host_stop, host_kept);
+    return rc != RTW_OK ? rc : accum_export(a, host_sums, host_squares, host_stop, host_kept);
+}
+
+extern "C" RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                              const float* host_squares, const uint32_t* host_stop,
+                                              const uint32_t* host_kept) {
+    if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    const int rc = state_pointers(a, host_squares, host_stop, host_kept);
+    return rc != RTW_OK ? rc : accum_import(a, info, host_sums, host_squares, host_stop, host_kept);
+}
+
+extern "C" RTW_API int rtw_accum_resolve_kept(rtw_accum* a, uint32_t* d_out, void* stream) {
+    return accum_resolve(a, (float*)d_out, (hipStream_t)stream, 3);
 }
 
 extern "C" RTW_API int rtw_accum_tile_stops(rtw_accum* a, uint32_t* host_stop) {
@@ -5699,8 +5938,14 @@ extern "C" RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_
     int rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
     const uint32_t waves = RTW_ADAPT_BLOCK / 64;
-    hipLaunchKernelGGL(adapt_tiles_kernel, dim3((a->tiles + waves - 1) / waves), dim3(RTW_ADAPT_BLOCK), 0, stream,
-                       (const float*)a->sums, (const float*)a->squares, G, a->info.samples, target, min_samples, a->tile_stop);
+    if (a->kept)
+        hipLaunchKernelGGL(adapt_tiles_finite_kernel, dim3((a->tiles + waves - 1) / waves), dim3(RTW_ADAPT_BLOCK), 0, stream,
+                           (const float*)a->sums, (const float*)a->squares, (const uint32_t*)a->kept, G, a->info.samples,
+                           target, min_samples, a->tile_stop);
+    else
+        hipLaunchKernelGGL(adapt_tiles_kernel, dim3((a->tiles + waves - 1) / waves), dim3(RTW_ADAPT_BLOCK), 0, stream,
+                           (const float*)a->sums, (const float*)a->squares, G, a->info.samples, target, min_samples,
+                           a->tile_stop);
     HIP_TRY(hipGetLastError());
     rc = accum_leave(a, stream);
     if (rc != RTW_OK) return rc;
@@ -5723,6 +5968,22 @@ extern "C" RTW_API int rtw_adapt_tiles_host(const float* sums, const float* squa
                                             uint32_t samples, float target, uint32_t min_samples, uint32_t* tile_stop) {
     if (!sums || !squares || !params || !tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (rtw_adapt_tiles(sums, squares, params, samples, target, min_samples, tile_stop) != 0)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the stop test needs samples >= 2, min_samples >= 2 and a frame's geometry");
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_finite_accumulate_host(const float* colors, uint32_t n_samples, uint32_t total, float* sums,
+                                                  float* squares, uint32_t* kept) {
+    if (!colors || !sums || !kept) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    rtw_finite_accumulate(colors, n_samples, total, sums, squares, kept);
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_adapt_tiles_finite_host(const float* sums, const float* squares, const uint32_t* kept,
+                                                   const rtw_render_params* params, uint32_t samples, float target,
+                                                   uint32_t min_samples, uint32_t* tile_stop) {
+    if (!sums || !squares || !kept || !params || !tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (rtw_adapt_tiles_finite(sums, squares, kept, params, samples, target, min_samples, tile_stop) != 0)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the stop test needs samples >= 2, min_samples >= 2 and a frame's geometry");
     return RTW_OK;
 }

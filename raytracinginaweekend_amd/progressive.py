@@ -13,6 +13,14 @@ tiles only.  A stopped tile stays stopped; it holds, bit for bit, the pixels of 
 samples_per_pixel = its own count (`tile_stops()`, `sample_counts()`), so the image stays exact tile by
 tile, with the stop map as part of the output.  `render_adaptive` is the loop.
 
+With ``finite=True`` the accumulate pass leaves out every sample with a NaN or infinite channel (the reference's
+0/0 pdf quirk makes an occasional whole sample NaN, and one such sample turns a plain accumulator's pixel NaN for
+good): the sample adds nothing and is not counted, `kept_counts()` holds the samples that entered each pixel's sum
+and `rejected_counts()` the rest, and `image()`, `stderr()`, `noise()`, `adapt()` and `denoised()` divide by the
+pixel's own kept count.  On a pixel with no rejected sample every value is the plain accumulator's, bit for bit.
+Dropping samples biases the estimate (the dropped paths carried energy): a plain accumulator's `image()` and
+`render` stay the exact reference image.  Combines with moments and adaptive.  `render_finite` is the one-call form.
+
 The reference's thread_count > 1 splits a frame's samples into planes by the *final* spp
 (split_work_tasks, rendering.rs:222-237), so a prefix of such a frame is not a frame: accumulators
 render thread_count 1 only.
@@ -45,7 +53,8 @@ class AccumState:
     """One accumulator's exported state: the fields of rtw_accum_info, the per-slot sums and, with
     moments, the sums of squares (float32, shape (slots, 3); padding slots of edge tiles hold zeros);
     of an adaptive accumulator also the stop map (uint32, shape (tiles,), tiles = slots / (tile_width *
-    tile_height): 0 = active, else the sample count the tile stopped at)."""
+    tile_height): 0 = active, else the sample count the tile stopped at); of a finite accumulator also the kept
+    counts (uint32, shape (slots,): the samples that entered each slot's sums; padding slots hold 0)."""
 
     version: int
     flags: int
@@ -65,6 +74,7 @@ class AccumState:
     sums: np.ndarray
     squares: np.ndarray | None = None
     tile_stop: np.ndarray | None = None
+    kept: np.ndarray | None = None
 
     def header(self) -> dict:
         return {n: int(getattr(self, n)) for n in _HEADER}
@@ -76,7 +86,7 @@ class AccumState:
 
     def save(self, path) -> None:
         """One .npz of plain arrays (numpy.savez): a 0-d array per header field, `sums`, `squares`
-        when the accumulator kept moments, and `tile_stop` when it was adaptive."""
+        when the accumulator kept moments, `tile_stop` when it was adaptive and `kept` when it was finite."""
         arrays = {n: np.asarray(getattr(self, n), dtype=t) for n, t in _HEADER.items()}
         arrays["sums"] = np.ascontiguousarray(self.sums, np.float32)
         if self.squares is not None:
@@ -86,6 +96,11 @@ class AccumState:
             if stop.dtype != np.uint32 or stop.shape != (self.tiles,):
                 raise ValueError("tile_stop is not uint32 of shape (tiles,)")
             arrays["tile_stop"] = np.ascontiguousarray(stop)
+        if self.kept is not None:
+            kept = np.asarray(self.kept)
+            if kept.dtype != np.uint32 or kept.shape != (int(self.slots),):
+                raise ValueError("kept is not uint32 of shape (slots,)")
+            arrays["kept"] = np.ascontiguousarray(kept)
         with open(path, "wb") as f:
             np.savez(f, **arrays)
 
@@ -95,7 +110,7 @@ class AccumState:
         arrays `save` writes is refused."""
         with np.load(path, allow_pickle=False) as z:
             names = set(z.files)
-            known = set(_HEADER) | {"sums", "squares", "tile_stop"}
+            known = set(_HEADER) | {"sums", "squares", "tile_stop", "kept"}
             if names - known:
                 raise ValueError(f"not an accumulator checkpoint: unexpected entries {sorted(names - known)}")
             missing = (set(_HEADER) | {"sums"}) - names
@@ -120,7 +135,13 @@ class AccumState:
                 if a.dtype != np.uint32 or a.shape != (vals["slots"] // max(1, vals["tile_width"] * vals["tile_height"]),):
                     raise ValueError("accumulator checkpoint: tile_stop is not uint32 of shape (tiles,)")
                 arrays["tile_stop"] = a
-        return cls(**vals, sums=arrays["sums"], squares=arrays.get("squares"), tile_stop=arrays.get("tile_stop"))
+            if "kept" in names:
+                a = z["kept"]
+                if a.dtype != np.uint32 or a.shape != (vals["slots"],):
+                    raise ValueError("accumulator checkpoint: kept is not uint32 of shape (slots,)")
+                arrays["kept"] = a
+        return cls(**vals, sums=arrays["sums"], squares=arrays.get("squares"), tile_stop=arrays.get("tile_stop"),
+                   kept=arrays.get("kept"))
 
 
 assert [f.name for f in fields(AccumState)][:len(_HEADER)] == [n for n, _ in N.AccumInfo._fields_]
@@ -143,7 +164,7 @@ class Accumulator:
     def __init__(self, world: World | DeviceWorld, size: Size2i, max_depth: int,
                  render_mode: RenderMode = RenderMode.Default, *, seed: int = DEFAULT_SEED, device: int = 0,
                  tile: tuple[int, int] = (8, 8), part: tuple[int, int] = (0, 1), layout: int = N.LAYOUT_IMAGE,
-                 moments: bool = False, adaptive: bool = False, thread_count: int = 1):
+                 moments: bool = False, adaptive: bool = False, finite: bool = False, thread_count: int = 1):
         self._h = None
         self._denoiser = None  # made by the first denoised()
         self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
@@ -151,10 +172,12 @@ class Accumulator:
         self.size = size
         self.adaptive = bool(adaptive)
         self.moments = bool(moments) or self.adaptive
+        self.finite = bool(finite)
         self.params = render_params(size, 0, max_depth, render_mode, seed, tile=tile, part=part, layout=layout,
                                     thread_count=thread_count)
         h = C.c_void_p()
         flags = (N.ACCUM_MOMENTS if self.moments else 0) | (N.ACCUM_ADAPTIVE if self.adaptive else 0)
+        flags |= N.ACCUM_FINITE if self.finite else 0
         check(lib().rtw_accum_create(self.dworld._h, C.byref(self.params), flags, C.byref(h)))
         self._h = h
         self._out = None
@@ -302,6 +325,16 @@ class Accumulator:
 
         return self._resolved(lib().rtw_accum_resolve_samples, 1, torch.int32).view(np.uint32)
 
+    def kept_counts(self) -> np.ndarray:
+        """The samples that entered each pixel's sums (finite=True), uint32, laid out as `sample_counts()`."""
+        import torch
+
+        return self._resolved(lib().rtw_accum_resolve_kept, 1, torch.int32).view(np.uint32)
+
+    def rejected_counts(self) -> np.ndarray:
+        """The samples of each pixel that were left out: `sample_counts()` - `kept_counts()` (finite=True)."""
+        return self.sample_counts() - self.kept_counts()
+
     @property
     def tiles(self) -> int:
         """Local tiles of the partition (entries of the stop map)."""
@@ -325,13 +358,19 @@ class Accumulator:
         i = self.info()
         sums = np.zeros((i.slots, 3), np.float32)
         squares = np.zeros((i.slots, 3), np.float32) if self.moments else None
-        stop = None
-        if self.adaptive:
+        stop = kept = None
+        if self.finite:  # the one pair for every flag combination
+            stop = np.zeros(self.tiles, np.uint32) if self.adaptive else None
+            kept = np.zeros(i.slots, np.uint32)
+            check(lib().rtw_accum_export_state(self._h, _f32p(sums), _f32p(squares) if squares is not None else None,
+                                               _u32p(stop) if stop is not None else None, _u32p(kept)))
+        elif self.adaptive:
             stop = np.zeros(self.tiles, np.uint32)
             check(lib().rtw_accum_export_adaptive(self._h, _f32p(sums), _f32p(squares), _u32p(stop)))
         else:
             check(lib().rtw_accum_export(self._h, _f32p(sums), _f32p(squares) if squares is not None else None))
-        return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, sums=sums, squares=squares, tile_stop=stop)
+        return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, sums=sums, squares=squares, tile_stop=stop,
+                          kept=kept)
 
     def load_state(self, state: AccumState) -> None:
         """Continue `state`'s frame here.  Raises RtwError naming the field when the state belongs to another
@@ -344,7 +383,16 @@ class Accumulator:
         if sums.size != 3 * state.slots or (squares is not None and squares.size != sums.size):
             raise ValueError("state arrays do not hold 3 * slots floats")
         sq = _f32p(squares) if squares is not None else None
-        if state.tile_stop is not None:
+        if self.finite or state.kept is not None:  # the one pair: it refuses what the flags do not call for
+            stop = None if state.tile_stop is None else np.ascontiguousarray(state.tile_stop, np.uint32)
+            kept = None if state.kept is None else np.ascontiguousarray(state.kept, np.uint32)
+            if stop is not None and stop.shape != (self.tiles,):
+                raise ValueError("state.tile_stop does not hold one entry per tile")
+            if kept is not None and kept.shape != (state.slots,):
+                raise ValueError("state.kept does not hold one entry per slot")
+            check(lib().rtw_accum_import_state(self._h, C.byref(i), _f32p(sums), sq, _u32p(stop) if stop is not None else None,
+                                               _u32p(kept) if kept is not None else None))
+        elif state.tile_stop is not None:
             stop = np.ascontiguousarray(state.tile_stop, np.uint32)
             if stop.shape != (self.tiles,):
                 raise ValueError("state.tile_stop does not hold one entry per tile")
@@ -371,9 +419,24 @@ def render_progressive(size: Size2i, max_depth: int, world, batches, **kw):
         acc.release()
 
 
+def render_finite(size: Size2i, spp: int, max_depth: int, world, **kw):
+    """`spp` samples per pixel through a finite accumulator: returns (image, rejected), the mean of each pixel's
+    finite samples ((W*H, 3) f32; +0 where none was finite) and the samples left out per pixel ((W*H, 1) uint32)."""
+    if spp < 1:
+        raise ValueError("spp must be >= 1")
+    kw["finite"] = True
+    acc = Accumulator(world, size, max_depth, **kw)
+    try:
+        acc.add(spp)
+        return acc.image(), acc.rejected_counts()
+    finally:
+        acc.release()
+
+
 def render_to_noise(size: Size2i, max_depth: int, world, target: float, max_samples: int, batch: int = 16, **kw):
     """Adds `batch` samples at a time (the last batch cut to `max_samples`) until noise() <= target or
-    samples == max_samples.  Returns (image, samples, noise)."""
+    samples == max_samples.  Returns (image, samples, noise).  Keyword arguments go to `Accumulator` (finite=True
+    among them)."""
     if max_samples < 2 or batch < 1:
         raise ValueError("max_samples must be >= 2 and batch >= 1")
     kw["moments"] = True
@@ -397,7 +460,8 @@ def render_adaptive(size: Size2i, max_depth: int, world, target: float, max_samp
     `min_samples` on, stops the tiles whose worst pixel's relative standard error is at most `target`
     (`Accumulator.adapt`), until no tile is active or samples == max_samples.  Returns (image, sample_counts,
     info): info = {"samples": the frontier, "samples_rendered": the sum of the counts over the owned pixels,
-    "active_tiles", "noise"}.  Every tile of the image equals `render` at its own count."""
+    "active_tiles", "noise"}.  Every tile of the image equals `render` at its own count (with finite=True, passed
+    on to `Accumulator`: on the pixels without a rejected sample)."""
     if max_samples < 2 or batch < 1 or min_samples < 2:
         raise ValueError("max_samples and min_samples must be >= 2 and batch >= 1")
     kw["adaptive"] = True
