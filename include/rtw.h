@@ -469,6 +469,54 @@ RTW_API int rtw_accum_export_state(rtw_accum* a, float* host_sums, float* host_s
 RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                    const float* host_squares, const uint32_t* host_tile_stop, const uint32_t* host_kept);
 
+/* ---- partition records: accumulators across GPUs ------------------------------------------- */
+/* N accumulators of parts (0..N-1, N) of one frame, one per GPU, make the whole image's accumulator: each packs
+ * its state into a record, the records are gathered onto one device (one collective), and one launch places them
+ * into an accumulator of part (0, 1) there.  Sums, squares and kept are tile-major: local tile lt
+ * of part (r, N) is tile r + lt * N of the frame, and part (0, 1) holds tile t at local index t, so the merge is a
+ * placement of tile blocks.  Stop decisions are per tile and the RNG streams are keyed by (seed, pixel, sample):
+ * the merged accumulator is, bit for bit, the one a single GPU would hold.
+ *
+ * The record, in 4-byte words (include/rtw_parts.h has the arithmetic; S0 and T0 are the slots and tiles of part
+ * (0, N), which owns the most tiles, so all N records have one size and one set of section offsets):
+ *   header     8 words: record version (1), flags (RTW_ACCUM_*), part_index, part_count, samples, slots, tiles, 0
+ *   sums       3 * S0 f32
+ *   squares    3 * S0 f32   with RTW_ACCUM_MOMENTS
+ *   kept       S0 u32       with RTW_ACCUM_FINITE
+ *   tile_stop  T0 u32       with RTW_ACCUM_ADAPTIVE
+ * A section's words past the partition's own slots or tiles are zero.
+ *
+ * rtw_accum_packed_bytes: the bytes of one such record for params' frame (params' own part is not read) and
+ * part_count parts.  Host only. */
+RTW_API int rtw_accum_packed_bytes(const rtw_render_params* params, uint32_t flags, int32_t part_count, int64_t* bytes);
+/* Copies the accumulator's state into the device buffer d_packed (4-byte aligned, rtw_accum_packed_bytes for the
+ * accumulator's own part_count): header, sections, zeros in the tails.  Any accumulator, of any part and layout.
+ * Ordered with the accumulator's other calls; asynchronous on `stream`. */
+RTW_API int rtw_accum_pack(rtw_accum* a, void* d_packed, void* stream);
+/* Replaces all of `whole`'s state by the merge of part_count records, record r at d_gathered + r * stride_bytes
+ * (the shape rtw_untile_device takes; stride_bytes a multiple of 4, at least rtw_accum_packed_bytes).  `whole` is of
+ * part (0, 1).  First the headers are read back, after the work already on `stream` and after the calls already
+ * issued on whole's world (the packs of its other accumulators, on any stream), and refused with a message
+ * naming the field: stride_bytes; a record's version, flags (against whole's), part_index (record r holds part r),
+ * part_count, slots and tiles (against the arithmetic), reserved; samples, which must be equal in all records
+ * unless the flags hold RTW_ACCUM_ADAPTIVE.  With it whole's samples becomes the largest: rtw_accum_add does not
+ * count when every tile of a part has stopped, so such a part's count stays where its last tile stopped, and the
+ * largest is the count a single GPU would hold; its stop sections are read back too and a tile_stop of 1 or above
+ * its record's samples is refused as rtw_accum_import_adaptive refuses it.  kept is not checked value by value: it
+ * comes from accumulators, not from a file.  Nothing is launched or changed on a refusal.  Then one launch places
+ * every record's tile blocks; whole may be read (resolve, stderr, noise, adapt, export) or added to as if it had
+ * taken the samples itself.  The launch is asynchronous on `stream`; the call synchronizes it for the headers and,
+ * adaptive, once more for the host's copy of the stop map.  The records themselves are only read. */
+RTW_API int rtw_accum_merge_parts(rtw_accum* whole, const void* d_gathered, int64_t stride_bytes, int32_t part_count,
+                                  void* stream);
+/* The same merge on host arrays, without a GPU: `gathered` in the record layout above; sums and squares 3 * slots
+ * floats and kept slots entries of the whole image (slots = tiles * tile_width * tile_height), tile_stop its tiles;
+ * a pointer the flags call for is non-null and any other NULL.  *samples gets the merged count.  The same refusals;
+ * nothing is written on one. */
+RTW_API int rtw_accum_merge_parts_host(const rtw_render_params* params, uint32_t flags, const void* gathered,
+                                       int64_t stride_bytes, int32_t part_count, float* sums, float* squares,
+                                       uint32_t* kept, uint32_t* tile_stop, uint32_t* samples);
+
 /* ---- first-hit AOVs ------------------------------------------------------------------------- */
 /* An AOV accumulator keeps, per pixel of the whole image, running sums of what the camera rays hit first:
  * albedo, normal and depth.  An AOV sample is one camera ray and one closest hit, no bounce;

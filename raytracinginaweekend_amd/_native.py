@@ -334,7 +334,13 @@ _SIGS = {
                                          C.POINTER(C.c_uint32)]),
     "rtw_accum_import_state": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "rtw_finite_accumulate_host": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+    "rtw_accum_packed_bytes": (C.c_int, [C.POINTER(RenderParams), C.c_uint32, C.c_int32, C.POINTER(C.c_int64)]),
+    "rtw_accum_pack": (C.c_int, [_P, _P, _P]),
+    "rtw_accum_merge_parts": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
+    "rtw_accum_merge_parts_host": (C.c_int, [C.POINTER(RenderParams), C.c_uint32, _P, C.c_int64, C.c_int32,
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rtw_finite_accumulate_host":(C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtw_adapt_tiles_finite_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
                                               C.POINTER(RenderParams), C.c_uint32, C.c_float, C.c_uint32,
@@ -445,6 +451,13 @@ def check(rc: int) -> None:
     if rc != RTW_OK:
         msg = lib().rtw_last_error()
         raise RtwError(rc, msg.decode() if msg else "")
+
+
+def packed_bytes(params: RenderParams, flags: int, part_count: int) -> int:
+    """rtw_accum_packed_bytes: the bytes of one partition's packed accumulator record (host only)."""
+    n = C.c_int64()
+    check(lib().rtw_accum_packed_bytes(C.byref(params), flags, part_count, C.byref(n)))
+    return n.value
 
 
 def declared_symbols(header_path: str) -> list[str]:

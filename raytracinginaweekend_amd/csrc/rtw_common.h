@@ -16,6 +16,8 @@ struct rtw_rng {
     rtw_xoro s;
 };
 
+struct rtw_parts_layout;  // include/rtw_parts.h
+
 namespace rtw {
 
 // Thread-local last error (returned by rtw_last_error()).
@@ -39,5 +41,16 @@ int sah_build(const float* lo, const float* hi, int32_t n, std::vector<rtw_bvh_n
 int sah_build_split(const float* lo, const float* hi, const float* tri, const float* leaf_km, int32_t n, double budget,
                     std::vector<rtw_bvh_node>& nodes, std::vector<float>& km, int32_t* root, int* depth,
                     int depth_cap = 0);
+
+// The pack and merge launches of rtw_accum_pack / rtw_accum_merge_parts (rtw_parts.hip; the layout is
+// include/rtw_parts.h's).  Pointers the layout's flags do not call for are null.  The callers have validated
+// the sizes: the launches only choose the 16-byte or the dword path.
+hipError_t parts_pack_launch(const rtw_parts_layout& L, int32_t part_index, uint32_t samples, const float* sums,
+                             const float* squares, const uint32_t* kept, const uint32_t* stop, void* d_packed,
+                             hipStream_t stream);
+hipError_t parts_merge_launch(const rtw_parts_layout& L, const void* d_gathered, uint64_t stride_bytes, float* sums,
+                              float* squares, uint32_t* kept, uint32_t* stop, hipStream_t stream);
+// fail() with the message of a refused merge: the field's name and the record (at[0]) and local tile (at[1])
+int parts_refuse(const char* field, const int32_t at[2]);
 
 }  // namespace rtw

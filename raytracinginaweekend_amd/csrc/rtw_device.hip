@@ -37,6 +37,7 @@
 #include "../../include/rtw_beam.h"
 #include "../../include/rtw_adapt.h"
 #include "../../include/rtw_finite.h"
+#include "../../include/rtw_parts.h"
 #include "rtw_common.h"
 
 #ifndef RTW_BLOCK
@@ -5961,6 +5962,84 @@ extern "C" RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_
     a->active = active;
     *active_tiles = active;
     *active_pixels = pixels;
+    return RTW_OK;
+}
+
+// ---- partition records (rtw.h; include/rtw_parts.h).  The kernels are rtw_parts.hip's. ----
+extern "C" RTW_API int rtw_accum_pack(rtw_accum* a, void* d_packed, void* stream_) {
+    if (!a || !d_packed) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (((uintptr_t)d_packed & 3u) != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "d_packed must be 4-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    rtw_parts_layout L;
+    if (rtw_parts_layout_of(&a->p, a->info.flags, a->info.part_count, &L) != 0 ||
+        (uint32_t)rtw_parts_tiles(&L, a->info.part_index) != a->tiles)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
+    int rc = accum_enter(a, stream);
+    if (rc != RTW_OK) return rc;
+    HIP_TRY(rtw::parts_pack_launch(L, a->info.part_index, a->info.samples, a->sums, a->squares, a->kept, a->tile_stop, d_packed,
+                                   stream));
+    return accum_leave(a, stream);
+}
+
+extern "C" RTW_API int rtw_accum_merge_parts(rtw_accum* whole, const void* d_gathered, int64_t stride_bytes, int32_t part_count,
+                                             void* stream_) {
+    rtw_accum* a = whole;
+    if (!a || !d_gathered) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (a->info.part_index != 0 || a->info.part_count != 1)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "a merge fills the whole image's accumulator: part_index / part_count is not 0 / 1");
+    hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t flags = a->info.flags;
+    int32_t at[2] = {0, 0};
+    rtw_parts_layout L;
+    if (rtw_parts_layout_of(&a->p, flags, part_count, &L) != 0) return rtw::parts_refuse("params", at);
+    if ((uint32_t)L.n_tiles != a->tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
+    if (stride_bytes < (int64_t)(L.words * 4) || stride_bytes % 4 != 0 || ((uintptr_t)d_gathered & 3u) != 0)
+        return rtw::parts_refuse("stride_bytes", at);
+    // The headers (and, adaptive, the stop sections) come back first, after the work already on `stream` (the
+    // packs, or the collective that filled the buffer): everything is refused before anything is launched.
+    HIP_TRY(hipSetDevice(a->g->device));
+    const size_t own_words = RTW_PARTS_HEADER_WORDS + ((flags & RTW_ACCUM_ADAPTIVE) ? (size_t)L.tiles0 : 0);
+    std::vector<uint32_t> host((size_t)part_count * own_words);
+    // (entered first: packs of this world's accumulators are waited for whatever stream they ran on; a refusal
+    // below leaves nothing to undo, the stream has only waited)
+    int rc = accum_enter(a, stream);
+    if (rc != RTW_OK) return rc;
+    for (int32_t r = 0; r < part_count; ++r) {
+        const char* rec = (const char*)d_gathered + (size_t)r * (size_t)stride_bytes;
+        uint32_t* h = host.data() + (size_t)r * own_words;
+        HIP_TRY(hipMemcpyAsync(h, rec, RTW_PARTS_HEADER_WORDS * 4, hipMemcpyDeviceToHost, stream));
+        if ((flags & RTW_ACCUM_ADAPTIVE) && L.tiles0 > 0)
+            HIP_TRY(hipMemcpyAsync(h + RTW_PARTS_HEADER_WORDS, rec + L.stop * 4, (size_t)L.tiles0 * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    uint32_t samples = 0;
+    for (int32_t r = 0; r < part_count; ++r) {
+        const uint32_t* h = host.data() + (size_t)r * own_words;
+        at[0] = r;
+        if (const char* bad = rtw_parts_check_header(&L, r, h)) return rtw::parts_refuse(bad, at);
+        const uint32_t s = h[RTW_PARTS_H_SAMPLES];
+        if (!(flags & RTW_ACCUM_ADAPTIVE) && r > 0 && s != samples) return rtw::parts_refuse("samples", at);
+        samples = std::max(samples, s);
+        if (flags & RTW_ACCUM_ADAPTIVE)
+            for (int32_t lt = 0; lt < rtw_parts_tiles(&L, r); ++lt) {
+                const uint32_t v = h[RTW_PARTS_HEADER_WORDS + lt];
+                at[1] = lt;
+                if (v == 1u || v > s) return rtw::parts_refuse("tile_stop", at);
+            }
+    }
+    HIP_TRY(rtw::parts_merge_launch(L, d_gathered, (uint64_t)stride_bytes, a->sums, a->squares, a->kept, a->tile_stop, stream));
+    rc = accum_leave(a, stream);
+    if (rc != RTW_OK) return rc;
+    if (flags & RTW_ACCUM_ADAPTIVE) {  // the host's copy of the stop map and its zeros, as after an adapt
+        HIP_TRY(hipMemcpyAsync(a->h_stop.data(), a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        uint32_t active = 0;
+        for (uint32_t t = 0; t < a->tiles; ++t) active += a->h_stop[t] == 0 ? 1u : 0u;
+        a->active = active;
+    }
+    a->info.samples = samples;
     return RTW_OK;
 }
 

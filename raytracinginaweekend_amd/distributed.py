@@ -12,6 +12,10 @@ TileExchange holds the partition arithmetic and the gather/untile step for both 
 (RCCL + the untile kernel) and host tensors (gloo + untile_host, the CPU mirror used by the
 world-size-2 and -3 tests).  Reference: rendering.rs:222-252 (the reference merges per-thread planes
 in one process; here the ranks own disjoint pixels, so the merge is a placement).
+
+DistributedAccumulator is the same idea for progressive accumulators (progressive.py): every rank adds to its own
+partition's accumulator, and one gather of packed state records plus one merge launch (include/rtw_parts.h) gives
+rank 0 the whole image's accumulator, with its noise estimate, stop map, kept counts, denoiser and checkpoint.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .rendering import DeviceWorld, Size2i, partition_floats, render_params, untile_device
+from .rendering import DEFAULT_SEED, DeviceWorld, RenderMode, Size2i, partition_floats, render_params, untile_device
 from .world import World
 
 
@@ -151,3 +155,144 @@ class FrameRenderer:
 
     def pixels_this_rank(self) -> int:
         return self.xchg.pixels_this_rank()
+
+
+def gather_records(record, gathered, rank: int, world_size: int) -> None:
+    """The accumulators' one collective: every rank's packed record (progressive.py; all of one size) onto rank 0,
+    rank r's at gathered[r * len(record):] there; other ranks pass None.  Device tensors with RCCL, host tensors
+    with gloo, as `TileExchange.gather`."""
+    import torch.distributed as dist
+
+    if rank == 0:
+        dist.gather(record, list(gathered.view(world_size, -1).unbind(0)), dst=0)
+    else:
+        dist.gather(record, None, dst=0)
+
+
+class DistributedAccumulator:
+    """A progressive accumulator of one frame across the ranks of a process group (one process per GPU).
+
+    Rank r owns an `Accumulator` of part (r, world_size) in LAYOUT_TILES (`local`); rank 0 also owns `whole`, a
+    plain `Accumulator` of part (0, 1) on the same `DeviceWorld`.  `add` is local and asynchronous; `adapt` is the
+    local decision plus one all_reduce of the two counts (the decisions are per tile, so they are one GPU's);
+    `sync` packs every rank's state, gathers the records onto rank 0 with one collective and merges them into
+    `whole`, which then is, bit for bit, the accumulator one GPU would hold after the same calls: read it through
+    its own API (`image`, `stderr`, `noise`, `sample_counts`, `kept_counts`, `tile_stops`, `denoised`, `state`).
+    With the nccl backend the device tensors are gathered; with any other (gloo) the record is staged through a
+    host tensor on both sides, which also lets several ranks share one GPU.  world_size 1 is a pass-through
+    without a collective: `local` is `whole`.
+
+    `sync` may be called any number of times; adds after it continue the partitions (not `whole`)."""
+
+    def __init__(self, world: World | DeviceWorld, size: Size2i, max_depth: int, rank: int = 0, world_size: int = 1,
+                 device: int = 0, *, seed: int = DEFAULT_SEED, tile: tuple[int, int] = (8, 8), moments: bool = False,
+                 adaptive: bool = False, finite: bool = False, render_mode: RenderMode = RenderMode.Default):
+        import torch
+
+        from .progressive import Accumulator
+
+        if not 0 <= rank < world_size:
+            raise ValueError("rank must be within 0 .. world_size - 1")
+        self.torch = torch
+        self.rank, self.world_size = rank, world_size
+        self.dev = torch.device("cuda", device)
+        self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
+        kw = dict(seed=seed, device=device, tile=tile, moments=moments, adaptive=adaptive, finite=finite)
+        self.whole = Accumulator(self.dworld, size, max_depth, render_mode, **kw) if rank == 0 else None
+        if world_size == 1:
+            self.local = self.whole
+        else:
+            self.local = Accumulator(self.dworld, size, max_depth, render_mode, part=(rank, world_size),
+                                     layout=N.LAYOUT_TILES, **kw)
+            # (a stride of whole 16 bytes: every record of the gathered buffer takes the merge's 16-byte path)
+            self.stride_bytes = -(-self.local.packed_bytes() // 16) * 16
+            self.record = torch.zeros(self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
+            self.gathered = (torch.zeros(world_size * self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
+                             if rank == 0 else None)
+        tw, th = tile
+        self.frame_tiles = -(-size.width // tw) * -(-size.height // th)
+        self.adaptive = bool(adaptive)
+        self.samples = 0  # the group's frontier: the samples of the active tiles, as one GPU would count them
+        self.active_tiles = self.frame_tiles
+
+    def release(self) -> None:
+        for a in {id(a): a for a in (self.local, self.whole) if a is not None}.values():
+            a.release()
+        self.local = self.whole = None
+
+    def _stream(self) -> int:
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _device_collectives(self) -> bool:
+        import torch.distributed as dist
+
+        return dist.get_backend() == "nccl"
+
+    def add(self, n: int) -> None:
+        """The next `n` samples of this rank's pixels (asynchronous; adaptive: of its active tiles).  Like one
+        GPU's accumulator, an adaptive group whose tiles have all stopped adds nothing and does not count."""
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if self.adaptive and self.active_tiles == 0:
+            return
+        self.local.add(n, self._stream())
+        self.samples += n
+
+    def adapt(self, target: float, min_samples: int = 16) -> tuple[int, int]:
+        """`Accumulator.adapt` on this rank's tiles, then one all_reduce(SUM): (active tiles, active pixels) of the
+        group.  Every rank calls it."""
+        # (a rank without tiles, or one whose tiles stopped before, holds fewer samples than the stop test asks
+        # for only in the first case: it has nothing to decide)
+        t, p = self.local.adapt(target, min_samples, self._stream()) if self.local.tiles > 0 else (0, 0)
+        if self.world_size > 1:
+            import torch.distributed as dist
+
+            counts = self.torch.tensor([t, p], dtype=self.torch.int64, device=self.dev if self._device_collectives() else "cpu")
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+            t, p = (int(v) for v in counts.tolist())
+        self.active_tiles = t
+        return t, p
+
+    def sync(self):
+        """Pack, one gather onto rank 0, merge: returns `whole` on rank 0 and None elsewhere.  Every rank calls it."""
+        if self.world_size == 1:
+            return self.whole
+        self.local.pack_into(self.record, self._stream())
+        if self._device_collectives():
+            gather_records(self.record, self.gathered, self.rank, self.world_size)
+        else:  # stage through the host on both sides
+            host = self.record.cpu()
+            staged = self.torch.zeros(self.gathered.numel(), dtype=self.torch.int32) if self.rank == 0 else None
+            gather_records(host, staged, self.rank, self.world_size)
+            if self.rank == 0:
+                self.gathered.copy_(staged)
+        if self.rank != 0:
+            return None
+        self.whole.merge_parts(self.gathered, self.stride_bytes, self.world_size, self._stream())
+        return self.whole
+
+
+def render_adaptive_distributed(world: World | DeviceWorld, size: Size2i, max_depth: int, rank: int, world_size: int,
+                                device: int, target: float, max_samples: int, min_samples: int = 16, batch: int = 16, **kw):
+    """`render_adaptive` across a process group: add and adapt until the group has no active tile or the frontier
+    reaches `max_samples`, then one `sync`.  Rank 0 returns (image, sample_counts, info) as `render_adaptive` does,
+    bit for bit its values; the other ranks return None.  Keyword arguments go to `DistributedAccumulator`."""
+    if max_samples < 2 or batch < 1 or min_samples < 2:
+        raise ValueError("max_samples and min_samples must be >= 2 and batch >= 1")
+    kw["adaptive"] = True
+    acc = DistributedAccumulator(world, size, max_depth, rank, world_size, device, **kw)
+    try:
+        active = acc.frame_tiles
+        while active > 0 and acc.samples < max_samples:
+            acc.add(min(batch, max_samples - acc.samples))
+            if acc.samples >= min_samples:
+                active = acc.adapt(target, min_samples)[0]
+        whole = acc.sync()
+        if whole is None:
+            return None
+        counts = whole.sample_counts()
+        info = {"samples": whole.samples, "samples_rendered": int(counts.astype(np.int64).sum()), "active_tiles": active,
+                "noise": whole.noise()[0]}
+        return whole.image(), counts, info
+    finally:
+        acc.release()

@@ -25,6 +25,11 @@ The reference's thread_count > 1 splits a frame's samples into planes by the *fi
 (split_work_tasks, rendering.rs:222-237), so a prefix of such a frame is not a frame: accumulators
 render thread_count 1 only.
 
+Across GPUs (distributed.py has the rank wrapper): every rank holds an accumulator of part (rank, N); `pack_into`
+writes its state as one record (include/rtw_parts.h), the records are gathered, and `merge_parts` places them
+into an accumulator of part (0, 1), which then is, bit for bit, the accumulator one GPU would hold.
+`AccumState.merge` / `AccumState.split` do the same to checkpoints, so one written by N ranks resumes on M.
+
 `AccumState` (the checkpoint) needs neither a GPU nor librtw.so.
 """
 from __future__ import annotations
@@ -46,6 +51,35 @@ _U64 = ("seed", "world_fingerprint")
 _I64 = ("slots",)
 _HEADER = {**{n: np.uint32 for n in _U32}, **{n: np.int32 for n in _I32}, **{n: np.uint64 for n in _U64},
            **{n: np.int64 for n in _I64}}
+
+
+RECORD_VERSION = 1  # RTW_PARTS_VERSION
+RECORD_HEADER_WORDS = 8
+
+
+def record_layout(width: int, height: int, tile: tuple[int, int], flags: int, part_count: int) -> dict:
+    """The packed record of include/rtw_parts.h in numpy's terms: per_tile, n_tiles, tiles0, slots0, the word
+    offsets sums / squares / kept / stop (None: the flags do not call for the section) and words."""
+    tw, th = tile
+    per_tile = tw * th
+    n_tiles = -(-width // tw) * -(-height // th)
+    tiles0 = -(-n_tiles // part_count)
+    slots0 = tiles0 * per_tile
+    at = RECORD_HEADER_WORDS
+    lay = {"per_tile": per_tile, "n_tiles": n_tiles, "tiles0": tiles0, "slots0": slots0, "sums": at}
+    at += 3 * slots0
+    for name, flag, words in (("squares", N.ACCUM_MOMENTS, 3 * slots0), ("kept", N.ACCUM_FINITE, slots0),
+                              ("stop", N.ACCUM_ADAPTIVE, tiles0)):
+        lay[name] = at if flags & flag else None
+        at += words if flags & flag else 0
+    lay["words"] = at
+    return lay
+
+
+def _part_slots(n_tiles: int, per_tile: int, part: tuple[int, int]) -> tuple[np.ndarray, np.ndarray]:
+    """(the frame's tiles part (r, N) owns, the whole image's slots they are)."""
+    tiles = np.arange(part[0], n_tiles, part[1], dtype=np.int64)
+    return tiles, (tiles[:, None] * per_tile + np.arange(per_tile, dtype=np.int64)[None, :]).ravel()
 
 
 @dataclass
@@ -142,6 +176,123 @@ class AccumState:
                 arrays["kept"] = a
         return cls(**vals, sums=arrays["sums"], squares=arrays.get("squares"), tile_stop=arrays.get("tile_stop"),
                    kept=arrays.get("kept"))
+
+    def _frame_tiles(self) -> int:
+        return -(-int(self.width) // int(self.tile_width)) * -(-int(self.height) // int(self.tile_height))
+
+    @classmethod
+    def merge(cls, states) -> "AccumState":
+        """The whole image's state (part (0, 1)) from the states of parts (0..N-1, N) of one frame, in any order:
+        a placement of tile blocks, bit for bit the state one accumulator would hold.  Raises ValueError naming
+        the field when the states differ in geometry, max_depth, render_mode, seed, world_fingerprint, version or
+        flags, when a part is missing or comes twice, when slots or an array does not fit the part, and when
+        samples differ between parts that are not adaptive.  Adaptive: samples is the largest of the parts' (a
+        part whose tiles have all stopped no longer counts, `Accumulator.add`)."""
+        states = list(states)
+        if not states:
+            raise ValueError("merge needs at least one state")
+        first = states[0]
+        for s in states[1:]:
+            for n in ("version", "flags", "width", "height", "tile_width", "tile_height", "part_count", "max_depth",
+                      "render_mode", "reserved", "seed", "world_fingerprint"):
+                if int(getattr(s, n)) != int(getattr(first, n)):
+                    raise ValueError(f"the states are not parts of one frame: {n} differs")
+        count = max(1, int(first.part_count))
+        by_part = {}
+        for s in states:
+            if int(s.part_index) in by_part:
+                raise ValueError(f"part_index {int(s.part_index)} comes twice")
+            by_part[int(s.part_index)] = s
+        for r in range(count):
+            if r not in by_part:
+                raise ValueError(f"part_index {r} of part_count {count} is missing")
+        if len(by_part) != count:
+            raise ValueError(f"part_index outside 0 .. part_count - 1 ({count})")
+        flags = int(first.flags)
+        adaptive = bool(flags & N.ACCUM_ADAPTIVE)
+        per_tile, n_tiles = int(first.tile_width) * int(first.tile_height), first._frame_tiles()
+        slots = n_tiles * per_tile
+        sums = np.zeros((slots, 3), np.float32)
+        squares = np.zeros((slots, 3), np.float32) if flags & N.ACCUM_MOMENTS else None
+        kept = np.zeros(slots, np.uint32) if flags & N.ACCUM_FINITE else None
+        stop = np.zeros(n_tiles, np.uint32) if adaptive else None
+        samples = int(first.samples)
+        for r in range(count):
+            s = by_part[r]
+            tiles, at = _part_slots(n_tiles, per_tile, (r, count))
+            if int(s.slots) != at.size:
+                raise ValueError(f"part {r}: slots differs from the partition's ({at.size})")
+            if not adaptive and int(s.samples) != samples:
+                raise ValueError(f"part {r}: samples differs (only adaptive parts may differ)")
+            samples = max(samples, int(s.samples))
+            for name, dst, shape in (("sums", sums, (at.size, 3)), ("squares", squares, (at.size, 3)), ("kept", kept, (at.size,)),
+                                     ("tile_stop", stop, (tiles.size,))):
+                src = getattr(s, name)
+                if (src is None) != (dst is None):
+                    raise ValueError(f"part {r}: {name} does not go with the flags")
+                if dst is None:
+                    continue
+                src = np.asarray(src)
+                if src.shape != shape or src.dtype != dst.dtype:
+                    raise ValueError(f"part {r}: {name} is not {dst.dtype} of shape {shape}")
+                # (bit patterns, not values: a NaN's payload travels)
+                dst.view(np.uint32)[tiles if name == "tile_stop" else at] = src.view(np.uint32)
+            if adaptive:
+                bad = (s.tile_stop == 1) | (s.tile_stop > int(s.samples))
+                if bad.any():
+                    raise ValueError(f"part {r}: tile_stop[{int(np.flatnonzero(bad)[0])}] is 1 or above the part's samples")
+        head = first.header()
+        head.update(part_index=0, part_count=1, samples=samples, slots=slots)
+        return cls(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept)
+
+    def split(self, part_count: int) -> list["AccumState"]:
+        """The inverse of `merge`: the states of parts (0..part_count-1, part_count) of this whole-image state.  A
+        stopped tile keeps its stop; a part's samples is this state's when the part has an active tile (or the
+        state is not adaptive), else the largest stop among its tiles (0 for a part without tiles): what that
+        rank's accumulator would hold.  `merge(s.split(M))` is `s` for every M, so `merge` then `split(M)`
+        re-partitions a checkpoint of N ranks for M (each loads its part with `Accumulator.load_state`)."""
+        if (int(self.part_index), max(1, int(self.part_count))) != (0, 1):
+            raise ValueError("split needs the whole image's state: part_index / part_count is not 0 / 1")
+        if part_count < 1:
+            raise ValueError("part_count must be >= 1")
+        per_tile, n_tiles = int(self.tile_width) * int(self.tile_height), self._frame_tiles()
+        if int(self.slots) != n_tiles * per_tile:
+            raise ValueError("slots differs from the frame's")
+        if self.tile_stop is not None and n_tiles and (self.tile_stop != 0).all() and int(self.tile_stop.max()) != int(self.samples):
+            raise ValueError("samples is above the largest stop although every tile has stopped: no accumulator "
+                             "holds such a state, and its parts could not tell")
+        out = []
+        for r in range(part_count):
+            tiles, at = _part_slots(n_tiles, per_tile, (r, part_count))
+            stop = None if self.tile_stop is None else np.ascontiguousarray(self.tile_stop[tiles])
+            samples = int(self.samples)
+            if stop is not None and not (stop == 0).any():
+                samples = int(stop.max()) if stop.size else 0
+            head = self.header()
+            head.update(part_index=r, part_count=part_count, samples=samples, slots=int(at.size))
+            out.append(AccumState(**head, sums=np.ascontiguousarray(self.sums[at]),
+                                  squares=None if self.squares is None else np.ascontiguousarray(self.squares[at]),
+                                  tile_stop=stop, kept=None if self.kept is None else np.ascontiguousarray(self.kept[at])))
+        return out
+
+    def packed(self, stride_bytes: int | None = None) -> np.ndarray:
+        """This state as the record `Accumulator.pack_into` writes (uint32 words, include/rtw_parts.h), padded
+        with zeros to `stride_bytes`: what a rank without device-aware collectives sends."""
+        count = max(1, int(self.part_count))
+        lay = record_layout(int(self.width), int(self.height), (int(self.tile_width), int(self.tile_height)), int(self.flags), count)
+        words = lay["words"] if stride_bytes is None else stride_bytes // 4
+        if words < lay["words"] or (stride_bytes or 0) % 4:
+            raise ValueError("stride_bytes must be a multiple of 4 and at least the record's bytes")
+        rec = np.zeros(words, np.uint32)
+        rec[:RECORD_HEADER_WORDS] = (RECORD_VERSION, int(self.flags), int(self.part_index), count, int(self.samples),
+                                     int(self.slots), self.tiles, 0)
+        for name, arr in (("sums", self.sums), ("squares", self.squares), ("kept", self.kept), ("stop", self.tile_stop)):
+            if (arr is None) != (lay[name] is None):
+                raise ValueError(f"{name} does not go with the flags")
+            if arr is not None:
+                flat = np.ascontiguousarray(arr).view(np.uint32).ravel()
+                rec[lay[name]: lay[name] + flat.size] = flat
+        return rec
 
 
 assert [f.name for f in fields(AccumState)][:len(_HEADER)] == [n for n, _ in N.AccumInfo._fields_]
@@ -372,6 +523,30 @@ class Accumulator:
         return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, sums=sums, squares=squares, tile_stop=stop,
                           kept=kept)
 
+    def packed_bytes(self) -> int:
+        """The bytes of this accumulator's packed record (the same for every part of its part_count)."""
+        return N.packed_bytes(self.params, int(self.info().flags), max(1, self.params.part_count))
+
+    def pack_into(self, tensor, stream_ptr: int | None = None) -> None:
+        """Writes the accumulator's state as one packed record (include/rtw_parts.h) into the device tensor
+        (at least `packed_bytes()` bytes; asynchronous on `stream_ptr`, ordered with the accumulator's calls)."""
+        if not tensor.is_cuda or not tensor.is_contiguous() or tensor.numel() * tensor.element_size() < self.packed_bytes():
+            raise ValueError("pack_into needs a contiguous device tensor of at least packed_bytes() bytes")
+        check(lib().rtw_accum_pack(self._h, C.c_void_p(tensor.data_ptr()), C.c_void_p(stream_ptr or 0)))
+
+    def merge_parts(self, gathered, stride_bytes: int, part_count: int, stream_ptr: int | None = None) -> None:
+        """Replaces this whole-image accumulator's state (part (0, 1)) by the merge of `part_count` packed records,
+        record r at byte r * stride_bytes of the device tensor `gathered` (rtw_accum_merge_parts).  Raises
+        RtwError naming the field for records of another version, flags, order, part_count or geometry, a bad
+        stride, and unequal samples where not adaptive; nothing is launched then."""
+        need = max(0, part_count - 1) * stride_bytes + N.packed_bytes(self.params, int(self.info().flags), max(1, part_count))
+        if not gathered.is_cuda or not gathered.is_contiguous():
+            raise ValueError("merge_parts needs a contiguous device tensor")
+        if stride_bytes > 0 and gathered.numel() * gathered.element_size() < need:
+            raise ValueError(f"the gathered tensor holds fewer than the {need} bytes of {part_count} records")
+        check(lib().rtw_accum_merge_parts(self._h, C.c_void_p(gathered.data_ptr()), stride_bytes, part_count,
+                                          C.c_void_p(stream_ptr or 0)))
+
     def load_state(self, state: AccumState) -> None:
         """Continue `state`'s frame here.  Raises RtwError naming the field when the state belongs to another
         world, geometry, max_depth, render mode, seed or flags."""
@@ -399,6 +574,34 @@ class Accumulator:
             check(lib().rtw_accum_import_adaptive(self._h, C.byref(i), _f32p(sums), sq, _u32p(stop)))
         else:  # (refused by an adaptive accumulator: its state includes the stop map)
             check(lib().rtw_accum_import(self._h, C.byref(i), _f32p(sums), sq))
+
+
+def merge_parts_host(like: AccumState, gathered: np.ndarray, stride_bytes: int, part_count: int) -> AccumState:
+    """rtw_accum_merge_parts_host: the whole image's state from `part_count` packed records in the host array
+    `gathered` (record r at byte r * stride_bytes), without a GPU.  `like` is any state of the frame (a part's or
+    the whole's): its geometry and flags size the arrays, and its other header fields are carried over.  Raises
+    RtwError naming the field, as `Accumulator.merge_parts` does."""
+    flags = int(like.flags)
+    p = render_params(Size2i(int(like.width), int(like.height)), 0, int(like.max_depth), RenderMode(int(like.render_mode)),
+                      int(like.seed), tile=(int(like.tile_width), int(like.tile_height)))
+    per_tile, n_tiles = int(like.tile_width) * int(like.tile_height), like._frame_tiles()
+    slots = n_tiles * per_tile
+    buf = np.ascontiguousarray(gathered).view(np.uint8).ravel()
+    need = max(0, part_count - 1) * stride_bytes + N.packed_bytes(p, flags, max(1, part_count))
+    if stride_bytes > 0 and buf.size < need:
+        raise ValueError(f"the gathered array holds fewer than the {need} bytes of {part_count} records")
+    sums = np.zeros((slots, 3), np.float32)
+    squares = np.zeros((slots, 3), np.float32) if flags & N.ACCUM_MOMENTS else None
+    kept = np.zeros(slots, np.uint32) if flags & N.ACCUM_FINITE else None
+    stop = np.zeros(n_tiles, np.uint32) if flags & N.ACCUM_ADAPTIVE else None
+    samples = C.c_uint32()
+    check(lib().rtw_accum_merge_parts_host(C.byref(p), flags, C.c_void_p(buf.ctypes.data), stride_bytes, part_count,
+                                           _f32p(sums), _f32p(squares) if squares is not None else None,
+                                           _u32p(kept) if kept is not None else None,
+                                           _u32p(stop) if stop is not None else None, C.byref(samples)))
+    head = like.header()
+    head.update(part_index=0, part_count=1, samples=int(samples.value), slots=slots)
+    return AccumState(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept)
 
 
 def world_fingerprint(world: World) -> int:
