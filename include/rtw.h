@@ -293,9 +293,16 @@ RTW_API int rtw_world_kernel(rtw_gpu_world* gw, int* lds_mode, int* leaf_kinds, 
 /* The exact template name of that kernel, as profilers print it inside the demangled symbol
  * ("render_kernel<false, 1, 0, 0, false, false>": counting variant, LDS mode, leaf kinds, texture kinds,
  * generic leaf tables in LDS, whole-pixel work items), NUL-terminated into buf[0..cap); "" before the
- * first render.
+ * first render.  The leaf-list kernel's single-sample variants (WP false) carry a seventh place, their camera
+ * batch; its whole-pixel variants keep six:
+ * "render_kernel_pl<false, 1, 0, 0, false, false, true>"; RTW_CAMERA_BATCH=0 selects the "false" kernel.
  * RTW_ERR_INVALID_ARGUMENT if cap is too small.  Diagnostics only (bench.py matches PMC rows by it). */
 RTW_API int rtw_world_kernel_name(rtw_gpu_world* gw, char* buf, int cap);
+/* Tests: the camera batch's counters on `device`, summed over the render launches since the last reset:
+ * out3 = fills, records stored valid, records picked up valid.  The last two are equal, and equal to the
+ * samples rendered, when every work item was traced exactly once; kernels without the batch add nothing.
+ * Synchronous; reset != 0 zeroes them. */
+RTW_API int rtw_debug_park_counts(int device, unsigned long long* out3, int reset);
 /* The shape of this world's last frame (rtw_render_device / rtw_render on it): render-kernel launches,
  * whether the work items were whole pixels (1: samples summed in registers, no colour buffer, DESIGN.md
  * 5.5b; 0: single samples through the colour buffer), and the dynamic-fetch threshold it ran with (the

@@ -276,6 +276,9 @@ struct KArgs {
     const int32_t* pl_count;
     const int32_t* pl_list;
     int32_t pl_cap, pl_shade_min;
+    // the prepared camera rays of render_kernel_pl's CB variants: per resident wave RTW_PARK_GROUPS groups of
+    // 64 float4 ([wave][group][lane]); null in every other kernel
+    float4* park;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1494,17 +1497,23 @@ __device__ __forceinline__ Ray camera_ray(const rtw_camera& c, rtw_xoro& rng, fl
 // setup, jitter, camera ray with its UnitDisc), 6 shading's samplers (UnitSphere / UnitBall /
 // gen_bool / light direction), 7 colour store and cost bookkeeping.
 #ifdef RTW_PHASE_TIMING
-__device__ unsigned long long rtw_phase_cycles[8];
+// (sums 8..11, read by rtw_debug_phase_extra: 8 the camera rays' share of phase 2 -- the leaf-list scan, and the
+// whole set-up of an iteration in which no scattered ray starts; 10, 11 the refill rounds that handed out an
+// item and the PH_PIXEL lanes they found)
+#define RTW_PT_SUMS 12
+__device__ unsigned long long rtw_phase_cycles[RTW_PT_SUMS];
 __device__ __forceinline__ unsigned long long* pt_slot() {
-    __shared__ unsigned long long s[(RTW_BLOCK / 64) * 10];
-    return s + (threadIdx.x >> 6) * 10;
+    __shared__ unsigned long long s[(RTW_BLOCK / 64) * (RTW_PT_SUMS + 2)];
+    return s + (threadIdx.x >> 6) * (RTW_PT_SUMS + 2);
 }
-#define RTW_PT_DECL do { unsigned long long* s_ = pt_slot(); if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < 8; ++k_) s_[k_] = 0; s_[8] = clock64(); s_[9] = 0; } } while (0);
-#define RTW_PT(k) do { if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) { unsigned long long* s_ = pt_slot(); const unsigned long long now_ = clock64(); s_[s_[9]] += now_ - s_[8]; s_[8] = now_; s_[9] = (k); } } while (0)
-#define RTW_PT_FLUSH do { RTW_PT(0); if ((threadIdx.x & 63) == 0) for (int k_ = 0; k_ < 8; ++k_) atomicAdd(&rtw_phase_cycles[k_], pt_slot()[k_]); } while (0)
+#define RTW_PT_DECL do { unsigned long long* s_ = pt_slot(); if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < RTW_PT_SUMS; ++k_) s_[k_] = 0; s_[RTW_PT_SUMS] = clock64(); s_[RTW_PT_SUMS + 1] = 0; } } while (0);
+#define RTW_PT(k) do { if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) { unsigned long long* s_ = pt_slot(); const unsigned long long now_ = clock64(); s_[s_[RTW_PT_SUMS + 1]] += now_ - s_[RTW_PT_SUMS]; s_[RTW_PT_SUMS] = now_; s_[RTW_PT_SUMS + 1] = (k); } } while (0)
+#define RTW_PT_ROUND(leader, lanes) do { if ((int)(threadIdx.x & 63) == (leader)) { unsigned long long* s_ = pt_slot(); s_[10] += 1; s_[11] += (lanes); } } while (0)
+#define RTW_PT_FLUSH do { RTW_PT(0); if ((threadIdx.x & 63) == 0) for (int k_ = 0; k_ < RTW_PT_SUMS; ++k_) atomicAdd(&rtw_phase_cycles[k_], pt_slot()[k_]); } while (0)
 #else
 #define RTW_PT_DECL
 #define RTW_PT(k) do { } while (0)
+#define RTW_PT_ROUND(leader, lanes) do { } while (0)
 #define RTW_PT_FLUSH do { } while (0)
 #endif
 
@@ -1667,6 +1676,12 @@ __device__ __forceinline__ ShadeOut shade(const DWorld* __restrict__ wp, int32_t
 // atomics) and added here once per block at its end (as one global atomic per post, the counters cost
 // suzanne's 8-way shares 13 %: every block's drain contended on three addresses)
 __device__ unsigned long long rtw_drain_counts[3];
+// the camera batch's traffic (rtw_debug_park_counts; tests): fills, records stored valid, records picked up
+// valid -- the last two are equal, and equal to the launch's samples, when every item is traced exactly once
+__device__ unsigned long long rtw_park_counts[3];
+// a parked record: 5 groups of 16 bytes (origin + time; direction + te; inv + fast | phase << 8 | valid << 16;
+// the RNG state after the camera's draws; found, slot, sample)
+#define RTW_PARK_GROUPS 5
 
 #ifdef RTW_WAVE_TIMING  // experiment builds: per-wave start / end / queue-empty wall clocks of the last launch
 __device__ unsigned long long rtw_wave_times[3 * 8192];
@@ -2214,9 +2229,13 @@ __device__ __forceinline__ void sah_take(Trav& T, float t, int leaf) {
 // PL (render_kernel_pl): camera rays of tiles that have a leaf list (rtw_beam.h) find their closest hit by
 // testing the listed leaves instead of walking the SAH tree.  Plain-sphere SAH worlds in LDS mode 1 only; every
 // other variant compiles none of it.
-template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool PL = false>
+// CB (render_kernel_pl<.., true>): the wave prepares the camera rays of up to 64 consecutive items of its reserve
+// with all its lanes at once (stream, jitter, camera ray, reciprocals, the tile's list) and parks them in A.park;
+// a lane that finished a sample only picks a record up.  Single-sample items, no tuner, no counting.
+template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool PL = false, bool CB = false>
 __device__ __forceinline__ void render_body(const KArgs& A) {
     static_assert(!PL || (LDS == 1 && LK == LK_SPHERES && !GEN), "leaf lists: plain-sphere worlds, LDS mode 1");
+    static_assert(!CB || (PL && !WP && !STATS), "camera batch: the leaf-list kernel's single-sample variants");
     constexpr bool LDS_SCENE = LDS >= 1;
     // LDS: [scene: nodes (2 float4 each), leaf records (1 float4 each), cull constants (1 float2
     // per node)] [stack: depth x BLOCK]
@@ -2346,6 +2365,8 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
     uint64_t w_next = 0, w_end = 0;
     uint32_t wq = (blockIdx.x * (RTW_BLOCK / 64) + (threadIdx.x >> 6)) % RTW_QUEUES;
     uint32_t qfail = 0;           // consecutive queues found empty: RTW_QUEUES of them end the launch
+    uint32_t p_next = 0, p_count = 0;                   // (CB) the park's records [p_next, p_count) wait for a lane
+    uint32_t pk_fills = 0, pk_stored = 0, pk_picked = 0;  // (CB) rtw_park_counts, per wave
     unsigned long long pf_b = 0;  // the prefetched batch's base, in lane pf_lane (its atomic's result)
     uint64_t pf_size = 0;         // its size; 0: none in flight
     int pf_lane = 0;
@@ -2385,6 +2406,177 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
         if (__ballot(T.phase != PH_DONE) == 0) break;  // wave-uniform: every lane is done
         // 1. lanes without a pixel take the next items of the wave's reserve
         RTW_PT(1);
+        if constexpr (CB) {
+            // (CB) ... of the wave's park, which is filled from the reserve 64 items at a time.  Every round pops a
+            // record, or fills at least one item, or advances qfail; the queues are only found empty on an empty
+            // park, so the lanes turn to PH_DONE with nothing parked.
+            for (;;) {
+                const unsigned long long m = __ballot(T.phase == PH_PIXEL);
+                if (m == 0) break;
+                if (p_next == p_count) {  // wave-uniform: the park is empty
+                    if (qfail >= RTW_QUEUES) {
+#ifdef RTW_WAVE_TIMING
+                        {
+                            const uint32_t wv_ = (blockIdx.x * RTW_BLOCK + threadIdx.x) / 64;
+                            if (wv_ < 8192) atomicMin(&rtw_wave_dry[wv_], (unsigned long long)wall_clock64());
+                        }
+                        if (!wx_dry) wx_busy = (uint32_t)__popcll(__ballot(T.phase != PH_PIXEL));
+                        wx_dry = true;
+#endif
+                        if (T.phase == PH_PIXEL) T.phase = PH_DONE;
+                        continue;
+                    }
+                    const int leader = __ffsll((long long)m) - 1;
+                    bool empty = false, took = false;
+                    if (w_next == w_end) {  // reserve used up: take the prefetched batch (fetch one if none)
+                        if (pf_size == 0) prefetch(leader);
+                        const uint64_t base =
+                            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pf_b >> 32), pf_lane) << 32) |
+                            (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pf_b, pf_lane);
+                        const uint64_t size = pf_size;
+                        pf_size = 0;
+                        took = true;
+                        empty = base >= A.q_cap;
+                        w_next = empty ? A.q_cap : base;
+                        w_end = empty ? A.q_cap : min(base + size, A.q_cap);
+                    }
+                    const uint32_t left = (uint32_t)min((uint64_t)64, w_end - w_next);  // the fill's items
+                    const uint64_t first = w_next;
+                    w_next += left;
+                    if (left) RTW_PT_ROUND(leader, (uint64_t)__popcll(m));
+                    bool valid = false;
+                    if ((uint32_t)lane < left) {  // every lane, whatever its phase: item first + lane on temporaries
+                        const uint64_t loc = first + (uint32_t)lane;
+                        const uint64_t item = ((loc / RTW_QGRAN) * RTW_QUEUES + wq) * RTW_QGRAN + loc % RTW_QGRAN;
+                        uint32_t f_slot = 0, f_sample = 0;
+                        int32_t f_px = 0, f_py = 0;
+                        if (item < A.items) {  // else: a padding index of the last granule row
+                            const bool big = item < A.items_big;
+                            const uint32_t rel = (uint32_t)(big ? item : item - A.items_big);  // < 2^32
+                            uint32_t ck, c, lt, it;
+                            if (A.tile_perm) {  // tile-major in cost order: tile rank, chunk, pixel of the tile
+                                const uint32_t g = fdiv(rel, A.fd_rank);
+                                const uint32_t wi = rel - g * A.fd_rank.d;
+                                ck = fdiv(wi, A.fd_tile);
+                                it = wi - ck * A.fd_tile.d;
+                                lt = A.tile_perm[g];
+                                c = lt * A.fd_tile.d + it;
+                            } else {  // chunk-major: pass after pass over the slots
+                                ck = fdiv(rel, A.fd_total);
+                                c = rel - ck * A.total;
+                                lt = fdiv(c, A.fd_tile);
+                                it = c - lt * A.fd_tile.d;
+                            }
+                            const uint32_t tile = (uint32_t)A.part_index + lt * (uint32_t)A.part_count;
+                            const uint32_t ty = fdiv(tile, A.fd_tiles_x), iy = fdiv(it, A.fd_tile_w);
+                            f_px = (int32_t)((tile - ty * (uint32_t)A.tiles_x) * (uint32_t)A.tile_w + (it - iy * (uint32_t)A.tile_w));
+                            f_py = (int32_t)(ty * (uint32_t)A.tile_h + iy);
+                            valid = f_px < A.width && f_py < A.height;  // else: padding slot of an edge tile
+                            f_slot = c;
+                            f_sample = big ? A.s_begin + ck * A.chunk : A.s_split + ck;  // (chunk = 1)
+                        }
+                        float4* P = A.park + ((size_t)(blockIdx.x * (RTW_BLOCK / 64) + (threadIdx.x >> 6)) * RTW_PARK_GROUPS) * 64 + lane;
+                        if (valid) {
+                            RTW_PT(5);
+                            // rendering.rs:174-176: jitter (x then y), then Camera::ray (start_sample's expressions)
+                            const uint32_t f_pix = (uint32_t)(f_py * A.width + f_px);
+                            rtw_xoro f_rng = rtw_sample_stream(A.seed_key, f_pix, f_sample);
+                            const float jx = d_uniform_sample(A.ux, &f_rng);
+                            const float jy = d_uniform_sample(A.uy, &f_rng);
+                            Trav F;
+                            F.ray = camera_ray(w.wc->cam, f_rng, (float)f_px * A.sx + jx, (float)f_py * A.sy + jy);
+                            RTW_PT(8);
+                            // step 2's set-up of a fresh camera ray
+                            const RayPre rp = ray_pre(F.ray, A.mk_world != 0);
+                            F.fast = (rp.fast ? 8 : 0) | (F.ray.d.x > 0.0f ? 1 : 0) | (F.ray.d.y > 0.0f ? 2 : 0) | (F.ray.d.z > 0.0f ? 4 : 0);
+                            F.phase = PH_TRACE;
+                            F.te = F32_INF;
+                            F.found = -1;
+                            if (sah) {
+                                if (rp.fast) F.fast |= RTW_TF_SAH;
+                                else F.phase = PH_REF;
+                            }
+                            if (rp.fast && sah) {  // the tile's leaf list (the list scan of the kernels without CB)
+                                const uint32_t tile = (uint32_t)A.part_index + fdiv(f_slot, A.fd_tile) * (uint32_t)A.part_count;
+                                const int32_t n = A.pl_count[tile];
+                                if (n >= 0) {
+                                    const int32_t* __restrict__ L = A.pl_list + (size_t)tile * (uint32_t)A.pl_cap;
+                                    const float4* fast = smem + A.fast_off;
+                                    for (int32_t j = 0; j < n; ++j) {
+                                        const int32_t leaf = L[j];
+                                        float t;
+                                        if (sphere_t(fast[leaf], F.ray, 0.001f, F.te, t)) sah_take(F, t, leaf);
+                                    }
+                                    F.phase = PH_SHADE;
+                                }
+                            }
+                            RTW_PT(1);
+                            P[0 * 64] = make_float4(F.ray.o.x, F.ray.o.y, F.ray.o.z, F.ray.time);
+                            P[1 * 64] = make_float4(F.ray.d.x, F.ray.d.y, F.ray.d.z, F.te);
+                            P[2 * 64] = make_float4(rp.inv.x, rp.inv.y, rp.inv.z, __int_as_float(F.fast | (F.phase << 8) | (1 << 16)));
+                            P[3 * 64] = make_float4(__int_as_float((int)(uint32_t)f_rng.s0), __int_as_float((int)(uint32_t)(f_rng.s0 >> 32)),
+                                                    __int_as_float((int)(uint32_t)f_rng.s1), __int_as_float((int)(uint32_t)(f_rng.s1 >> 32)));
+                            P[4 * 64] = make_float4(__int_as_float(F.found), __int_as_float((int)f_slot), __int_as_float((int)f_sample), 0.0f);
+                        } else {
+                            P[2 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // an invalid record: consumed like any other
+                        }
+                    }
+                    if (left) {
+                        ++pk_fills;
+                        pk_stored += (uint32_t)__popcll(__ballot(valid));
+                        p_next = 0;
+                        p_count = left;
+                        // the records are written by the lanes of this wave that read them: wavefront scope
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    }
+                    if (empty) {  // wave-uniform: queue wq is used up (no batch in flight); try the next one
+                        wq = (wq + 1) % RTW_QUEUES;
+                        ++qfail;
+                        w_next = w_end = 0;
+                    } else if (took) {
+                        qfail = 0;
+                    }
+                    if (!left) continue;
+                }
+                // the pick-up: the PH_PIXEL lanes take the next records in lane order
+                const uint32_t avail = p_count - p_next;
+                bool got = false;
+                if (T.phase == PH_PIXEL) {
+                    const unsigned long long below = (lane == 0) ? 0ull : (m & (~0ull >> (64 - lane)));
+                    const uint32_t r = (uint32_t)__popcll(below);
+                    if (r < avail) {
+                        const float4* P = A.park + ((size_t)(blockIdx.x * (RTW_BLOCK / 64) + (threadIdx.x >> 6)) * RTW_PARK_GROUPS) * 64 + (p_next + r);
+                        const float4 q2 = P[2 * 64];
+                        const int32_t bits = __float_as_int(q2.w);
+                        if (bits >> 16) {
+                            const float4 q0 = P[0 * 64], q1 = P[1 * 64], q3 = P[3 * 64], q4 = P[4 * 64];
+                            T.ray.o = v3(q0.x, q0.y, q0.z);
+                            T.ray.time = q0.w;
+                            T.ray.d = v3(q1.x, q1.y, q1.z);
+                            T.te = q1.w;
+                            T.inv = v3(q2.x, q2.y, q2.z);
+                            T.fast = bits & 0xFF;
+                            T.phase = (bits >> 8) & 0xFF;
+                            T.rng.s0 = (uint64_t)(uint32_t)__float_as_int(q3.x) | ((uint64_t)(uint32_t)__float_as_int(q3.y) << 32);
+                            T.rng.s1 = (uint64_t)(uint32_t)__float_as_int(q3.z) | ((uint64_t)(uint32_t)__float_as_int(q3.w) << 32);
+                            T.found = __float_as_int(q4.x);
+                            slot = (uint32_t)__float_as_int(q4.y);
+                            sample = (uint32_t)__float_as_int(q4.z);
+                            T.node = (T.fast & RTW_TF_SAH) ? w.sah_root_c2 : w.root;
+                            T.sp = 0;
+                            pdot = dot(v3(0.0f, 1.0f, 0.0f), T.ray.d);  // background_color.rs:13 on the primary ray
+                            att = v3(1.0f, 1.0f, 1.0f);
+                            acc = v3(0.0f, 0.0f, 0.0f);
+                            depth = A.max_depth;
+                            got = true;
+                        }
+                    }
+                }
+                pk_picked += (uint32_t)__popcll(__ballot(got));
+                p_next += min((uint32_t)__popcll(m), avail);
+            }
+        } else
         for (;;) {
             const unsigned long long m = __ballot(T.phase == PH_PIXEL);
             if (m == 0) break;
@@ -2429,6 +2621,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
             const uint64_t left = min(need, w_end - w_next);  // the first `left` lanes get an item
             const uint64_t first = w_next;
             w_next += left;
+            if (left) RTW_PT_ROUND(leader, need);
             if (!tuned) {  // wave-uniform: the epoch of the items being handed out
                 const uint64_t e = fdiv((uint32_t)min(w_next * RTW_QUEUES, (uint64_t)0xFFFFFFFFu), A.fd_epoch);
                 if (e == 0) {
@@ -2535,6 +2728,9 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
             if (lane == __ffsll((long long)__ballot(1)) - 1)
                 atomicAdd(&A.stats[ST_COUNT + DB_REST_CYCLES], (unsigned long long)(c_trav - c_mark));
         }
+#ifdef RTW_PHASE_TIMING
+        if (PL && __ballot(fresh && !cam) == 0 && __ballot(fresh) != 0) RTW_PT(8);  // only camera rays start
+#endif
         if (fresh) {
             fresh = false;
             const RayPre rp = ray_pre(T.ray, A.mk_world != 0);
@@ -2553,12 +2749,13 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
             T.te = F32_INF;
             T.found = -1;
             if (STATS) st.c[ST_RAYS]++;
-            if constexpr (PL) {
+            if constexpr (PL && !CB) {  // (CB: the fill has resolved the camera rays)
                 // a camera ray of a listed tile: the tile's leaves through the walk's own sphere test and take(),
                 // te = inf at the start; it leaves as the walk would (PH_SHADE, RTW_TF_SAH, te = succ(t), the tie
                 // flag), an empty list as a miss.  The tile from the slot (slot = local tile x tile pixels + pixel):
                 // no register is kept for it.  Lanes of one wave almost always share the tile, but need not.
                 if (cam && rp.fast && sah) {
+                    RTW_PT(8);
                     const uint32_t tile = (uint32_t)A.part_index + fdiv(slot, A.fd_tile) * (uint32_t)A.part_count;
                     const int32_t n = A.pl_count[tile];
                     if (n >= 0) {
@@ -2572,6 +2769,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                         }
                         T.phase = PH_SHADE;
                     }
+                    RTW_PT(2);
                 }
             }
         }
@@ -2812,7 +3010,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                 }
 #endif
                 ++sample;
-                if (sample >= sample_end) {
+                if (CB || sample >= sample_end) {  // (CB: an item is one sample)
                     T.phase = PH_PIXEL;
                     if (WPX) {  // accumulate_kernel's last step, for this pixel
                         if (!STATS && A.slot_cost && pcost) atomicAdd(&A.slot_cost[slot], pcost);
@@ -2867,6 +3065,9 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
             if (c) atomicAdd(&rtw_drain_counts[threadIdx.x], (unsigned long long)c);
         }
     }
+    if constexpr (CB) {  // the wave's counts, one atomic instruction per wave
+        if (lane < 3) atomicAdd(&rtw_park_counts[lane], (unsigned long long)(lane == 0 ? pk_fills : lane == 1 ? pk_stored : pk_picked));
+    }
     RTW_PT_FLUSH;
 #ifdef RTW_WAVE_TIMING
     {
@@ -2914,6 +3115,13 @@ __global__ __launch_bounds__(RTW_BLOCK, RTW_MIN_WAVES_PER_SIMD) void render_kern
 template <bool STATS, int LDS, int LK, int TX, bool GEN = false, bool WP = false>
 __global__ __launch_bounds__(RTW_BLOCK, RTW_MIN_WAVES_PER_SIMD) void render_kernel_pl(KArgs A) {
     render_body<STATS, LDS, LK, TX, GEN, WP, true>(A);
+}
+// The single-sample product kernels carry a seventh argument, CB: the camera batch (render_body).  An overload
+// with seven explicit arguments, so that the whole-pixel and counting kernels above keep their six-place names.
+template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool CB>
+__global__ __launch_bounds__(RTW_BLOCK, RTW_MIN_WAVES_PER_SIMD) void render_kernel_pl(KArgs A) {
+    static_assert(!STATS && !WP, "seven places: the single-sample product kernels");
+    render_body<STATS, LDS, LK, TX, GEN, WP, true, CB>(A);
 }
 
 // The list builder: one tile per 64-thread group, every leaf tested by rtw_beam.h's rule (the host builder's
@@ -4250,6 +4458,9 @@ struct rtw_gpu_world {
     double pl_mean = 0.0;            // mean entries over the tiles that have a list
     double pl_build_ms = 0.0;        // the builder kernel's time (device events)
     int32_t last_pl = 0;             // the last render took render_kernel_pl
+    int32_t last_cb = 0;             // ... its camera-batch variant
+    float4* park = nullptr;          // the camera batch's records (launch_render grows it)
+    size_t park_bytes = 0;
     int32_t last_lists[3] = {0, 0, 0};  // pl_info of the last frame (zeros: the frame used no lists)
     double last_mean = 0.0;
     uint64_t fingerprint = 0;  // rtw_world_fingerprint of the uploaded world (accumulator checkpoints)
@@ -4298,6 +4509,20 @@ extern "C" RTW_API int rtw_debug_drain_counts(int device, unsigned long long* ou
     return RTW_OK;
 }
 
+// tests: the camera batch's counters (rtw_park_counts: fills, records stored valid, records picked up valid),
+// summed over the launches since the last reset
+extern "C" RTW_API int rtw_debug_park_counts(int device, unsigned long long* out3, int reset) {
+    if (!out3) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out3, HIP_SYMBOL(rtw_park_counts), 3 * sizeof(unsigned long long)));
+    if (reset) {
+        unsigned long long z[3] = {};
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rtw_park_counts), z, sizeof(z)));
+    }
+    return RTW_OK;
+}
+
 // experiment builds (-DRTW_PHASE_TIMING): read and reset the phase cycle sums
 extern "C" RTW_API int rtw_debug_phase_cycles(unsigned long long* out8) {
 #ifdef RTW_PHASE_TIMING
@@ -4308,6 +4533,22 @@ extern "C" RTW_API int rtw_debug_phase_cycles(unsigned long long* out8) {
     return RTW_OK;
 #else
     (void)out8;
+    return rtw::fail(RTW_ERR_UNSUPPORTED, "built without RTW_PHASE_TIMING");
+#endif
+}
+
+// ... and the sums 8..11 (camera set-up cycles, unused, refill rounds, refill lanes); call it before
+// rtw_debug_phase_cycles, whose total they are not part of
+extern "C" RTW_API int rtw_debug_phase_extra(unsigned long long* out4) {
+#ifdef RTW_PHASE_TIMING
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out4, HIP_SYMBOL(rtw_phase_cycles), 4 * sizeof(unsigned long long),
+                                8 * sizeof(unsigned long long)));
+    unsigned long long z[4] = {};
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rtw_phase_cycles), z, sizeof(z), 8 * sizeof(unsigned long long)));
+    return RTW_OK;
+#else
+    (void)out4;
     return rtw::fail(RTW_ERR_UNSUPPORTED, "built without RTW_PHASE_TIMING");
 #endif
 }
@@ -4751,8 +4992,10 @@ extern "C" RTW_API int rtw_world_kernel_name(rtw_gpu_world* g, char* buf, int ca
     if (!g || !buf || cap < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     char s[64] = "";
     if (g->last_kernel[0] >= 0)  // the product kernel: render_kernel<STATS = false, LDS, LK, TX, GEN, WP>
-        std::snprintf(s, sizeof(s), "render_kernel%s<false, %d, %d, %d, %s, %s>", g->last_pl ? "_pl" : "", g->last_kernel[0], g->last_kernel[1],
-                      g->last_kernel[2], g->last_kernel[4] ? "true" : "false", g->last_kernel[5] ? "true" : "false");
+        std::snprintf(s, sizeof(s), "render_kernel%s<false, %d, %d, %d, %s, %s%s>", g->last_pl ? "_pl" : "", g->last_kernel[0], g->last_kernel[1],
+                      g->last_kernel[2], g->last_kernel[4] ? "true" : "false", g->last_kernel[5] ? "true" : "false",
+                      // (the trailing CB of render_kernel_pl's single-sample kernels)
+                      !g->last_pl || g->last_kernel[5] ? "" : g->last_cb ? ", true" : ", false");
     if ((int)std::strlen(s) >= cap) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "buffer too small");
     std::memcpy(buf, s, std::strlen(s) + 1);
     return RTW_OK;
@@ -4833,6 +5076,7 @@ extern "C" RTW_API int rtw_world_release(rtw_gpu_world* g) {
     if (g->arena) (void)hipFree(g->arena);
     if (g->queue) (void)hipFree(g->queue);
     if (g->colors) (void)hipFree(g->colors);
+    if (g->park) (void)hipFree(g->park);
     if (g->tune) (void)hipFree(g->tune);
     if (g->slot_cost) (void)hipFree(g->slot_cost);
     if (g->tile_buf) (void)hipFree(g->tile_buf);
@@ -4909,6 +5153,7 @@ size_t env_size(const char* name, size_t dflt);
 // acc_wp: an accumulator's add with whole-pixel items (KArgs::whole_pixel); RTW_ACC_NO_WP, before anything is
 // launched, when the world takes a GEN kernel, whose whole-pixel code cannot continue a sum
 constexpr int RTW_ACC_NO_WP = -1;
+int grow(void** buf, size_t* have, size_t need);
 int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool acc_wp = false) {
     const bool stats = kind == LK_STATS;
     const bool ktree = stats && A.stats_tree == 1;  // count the product kernel's own traversal
@@ -4937,7 +5182,7 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
     const int blocks_per_cu = std::max(1, (4 * RTW_MIN_WAVES_PER_SIMD * 64) / RTW_BLOCK);
     size_t cap = std::min({(size_t)RTW_LDS_SCENE_MAX, (size_t)g->lds_max, (size_t)g->lds_cu / blocks_per_cu});
 #ifdef RTW_PHASE_TIMING
-    cap -= (RTW_BLOCK / 64) * 10 * sizeof(unsigned long long);  // the per-wave phase sums (pt_slot)
+    cap -= (RTW_BLOCK / 64) * (RTW_PT_SUMS + 2) * sizeof(unsigned long long);  // the per-wave phase sums (pt_slot)
 #endif
     const size_t stack_bytes = (size_t)g->depth * RTW_BLOCK * sizeof(int32_t);
     const size_t stack16_bytes = stack_bytes / 2;  // 16-bit entries
@@ -5065,13 +5310,22 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
                      : fns[wp][tx][lk][mode];
     // the primary rays' leaf lists (render_frame_body offers them): the plain-sphere SAH walk in LDS mode 1
     static const KFn fns_pl[2][2] = {
-        {render_kernel_pl<false, 1, LK_SPHERES, TX_SOLID, false, false>, render_kernel_pl<false, 1, LK_SPHERES, TX_ANY, false, false>},
+        {render_kernel_pl<false, 1, LK_SPHERES, TX_SOLID, false, false, false>, render_kernel_pl<false, 1, LK_SPHERES, TX_ANY, false, false, false>},
         {render_kernel_pl<false, 1, LK_SPHERES, TX_SOLID, false, true>, render_kernel_pl<false, 1, LK_SPHERES, TX_ANY, false, true>}};
     // (the counting variant follows them when it counts the product kernel's own traversal, stats_tree 1)
     const bool pl = (!stats || ktree) && !gen && A.pl_count != nullptr && sah && lk == LK_SPHERES && mode == 1;
     if (pl) kf = stats ? render_kernel_pl<true, 1, LK_SPHERES, TX_ANY> : fns_pl[wp][tx];
     else A.pl_count = nullptr;
+    // ... with the camera batch where the single-sample kernel runs untuned on one-sample items
+    // (RTW_CAMERA_BATCH=0: the kernel without it)
+    static const KFn fns_cb[2] = {render_kernel_pl<false, 1, LK_SPHERES, TX_SOLID, false, false, true>,
+                                  render_kernel_pl<false, 1, LK_SPHERES, TX_ANY, false, false, true>};
+    const char* cbe = std::getenv("RTW_CAMERA_BATCH");
+    const bool cb = pl && !stats && !wp && A.tune == nullptr && A.chunk == 1 && !(cbe && cbe[0] == '0');
+    if (cb) kf = fns_cb[tx];
+    A.park = nullptr;
     if (!stats) {
+        g->last_cb = cb ? 1 : 0;
         g->last_pl = pl ? 1 : 0;
         g->last_kernel[0] = mode;
         g->last_kernel[1] = lk;
@@ -5087,6 +5341,12 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
     if (per_cu < 1) return rtw::fail(RTW_ERR_UNSUPPORTED, "render kernel does not fit on a CU");
     const int64_t want = (int64_t)((A.items + RTW_BLOCK - 1) / RTW_BLOCK);
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)per_cu * g->cus));
+    if (cb) {  // the park: one record per lane of every resident wave (every launch starts on an empty park)
+        const int rc = grow((void**)&g->park, &g->park_bytes,
+                            (size_t)blocks * (RTW_BLOCK / 64) * RTW_PARK_GROUPS * 64 * sizeof(float4));
+        if (rc != RTW_OK) return rc;
+        A.park = g->park;
+    }
     HIP_TRY(hipMemsetAsync(A.queue, 0, RTW_QUEUE_BLOCK * sizeof(unsigned long long), stream));
     // tuning epochs: whole passes over the slots, at least 2x the resident lanes in items (the
     // items in flight blur epoch boundaries; mirrored candidates cancel the blur's bias); explore

@@ -196,6 +196,13 @@ class DeviceWorld:
         out.update(self._lists())  # the primary rays' leaf lists of the last frame
         return out
 
+    def park_counts(self, reset: bool = True) -> tuple:
+        """(fills, records stored, records picked up) of the camera batch on this world's device, summed over
+        the render launches since the last reset (rtw_debug_park_counts; tests)."""
+        buf = (C.c_ulonglong * 3)()
+        check(lib().rtw_debug_park_counts(self.device, buf, 1 if reset else 0))
+        return tuple(int(v) for v in buf)
+
     def last_frame(self) -> dict:
         """The shape of the last frame: render launches, whole-pixel work items (no colour buffer),
         and the dynamic-fetch threshold it ran with (the tuned one once chosen, else the default)."""

@@ -41,16 +41,32 @@ def main():
     out = torch.empty(a.width * a.height * 3, dtype=torch.float32, device="cuda:0")
     dw.render_into(p, out.data_ptr(), 0)  # warm-up: tuning frame
     torch.cuda.synchronize()
+    fx = lib.rtw_debug_phase_extra
+    fx.restype = C.c_int
+    fx.argtypes = [C.POINTER(C.c_ulonglong)]
+    ext = (C.c_ulonglong * 4)()
+    fx(ext)
     fn(buf)
     dw.render_into(p, out.data_ptr(), 0)
     torch.cuda.synchronize()
-    if fn(buf) != 0:
+    if fx(ext) != 0 or fn(buf) != 0:
         raise SystemExit("library built without RTW_PHASE_TIMING")
     names = {1: "refill", 2: "traversal setup", 3: "traversal", 4: "shading", 5: "sample start",
              6: "samplers", 7: "stores"}
     tot = sum(buf[k] for k in names)
     print(a.scene, f"{a.width}x{a.height}x{a.spp}", " ".join(f"{names[k]} {buf[k] / tot:.4f}" for k in names),
           f"(wave cycles {tot})", flush=True)
+    # the leaf-list kernel's camera share of phase 2 (kept apart from the sums above: add it to the total), and
+    # the PH_PIXEL lanes a refill round finds (rounds that handed out at least one item)
+    tot += ext[0]
+    cam, rounds, lanes = ext[0], ext[2], ext[3]
+    mean = lanes / rounds if rounds else 0.0
+    share = (buf[1] + buf[5] + cam) / tot
+    print(f"with the camera set-up: refill {buf[1] / tot:.4f} setup(bounce) {buf[2] / tot:.4f} "
+          f"setup(camera) {cam / tot:.4f} sample start {buf[5] / tot:.4f} (wave cycles {tot})")
+    print(f"refill rounds {rounds} lanes {lanes} mean lanes {mean:.2f} of 64")
+    print(f"projection: ({share:.4f}) x (1 - {mean:.2f} / 64) = {share * (1.0 - mean / 64.0):.4f} of the wave cycles",
+          flush=True)
 
 
 if __name__ == "__main__":
