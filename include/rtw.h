@@ -290,6 +290,13 @@ RTW_API int rtw_world_tuning(rtw_gpu_world* gw, int* trace_min);
  * the reference-order proof and fallback); -1 each before the first render.
  * Diagnostics only. */
 RTW_API int rtw_world_kernel(rtw_gpu_world* gw, int* lds_mode, int* leaf_kinds, int* tex_kinds, int* tree);
+/* Where that launch put its tables: out[0] shading tables (leaf_info, materials) in LDS, out[1] texture
+ * table in LDS, out[2] the SAH walk's proof boxes in LDS, out[3] the generic leaf tables (transforms,
+ * spheres, boxes) in LDS, out[4] the shared drain's mailbox present (each 1 or 0; 0: read from HBM / L2, or
+ * no mailbox), out[5] the triangle prefix (leading mesh leaves whose records the kernel makes up), out[6]
+ * the launch's dynamic LDS bytes, out[7] 1 when it walked the SAH tree; -1 each before the first render.
+ * Diagnostics only. */
+RTW_API int rtw_world_last_launch_lds(rtw_gpu_world* gw, int32_t out[8]);
 /* The exact template name of that kernel, as profilers print it inside the demangled symbol
  * ("render_kernel<false, 1, 0, 0, false, false>": counting variant, LDS mode, leaf kinds, texture kinds,
  * generic leaf tables in LDS, whole-pixel work items), NUL-terminated into buf[0..cap); "" before the

@@ -4446,6 +4446,8 @@ struct rtw_gpu_world {
     // LDS mode, leaf kinds, texture kinds, tree, GEN (generic leaf tables in LDS), WP (whole-pixel items) of
     // the last render
     int32_t last_kernel[6] = {-1, -1, -1, -1, -1, -1};
+    // where that launch put its tables (rtw_world_last_launch_lds)
+    int32_t last_lds[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     // the last frame: render launches, whole-pixel items, the default threshold, in-frame tuning on
     int32_t last_frame[4] = {-1, -1, -1, 0};
     // the primary rays' per-tile leaf lists (rtw_beam.h, ensure_primary_lists): built on the device on the first
@@ -4988,6 +4990,12 @@ extern "C" RTW_API int rtw_world_kernel(rtw_gpu_world* g, int* lds_mode, int* le
     return RTW_OK;
 }
 
+extern "C" RTW_API int rtw_world_last_launch_lds(rtw_gpu_world* g, int32_t out[8]) {
+    if (!g || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    for (int i = 0; i < 8; ++i) out[i] = g->last_lds[i];
+    return RTW_OK;
+}
+
 extern "C" RTW_API int rtw_world_kernel_name(rtw_gpu_world* g, char* buf, int cap) {
     if (!g || !buf || cap < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     char s[64] = "";
@@ -5333,6 +5341,14 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
         g->last_kernel[3] = sah ? 1 : 0;
         g->last_kernel[4] = gen ? 1 : 0;
         g->last_kernel[5] = gen ? 0 : wp;  // (the template argument: GEN kernels take either kind of item)
+        g->last_lds[0] = A.sh_li >= 0 ? 1 : 0;
+        g->last_lds[1] = A.sh_tex0 >= 0 ? 1 : 0;
+        g->last_lds[2] = A.sh_box >= 0 ? 1 : 0;
+        g->last_lds[3] = A.sh_xf >= 0 ? 1 : 0;
+        g->last_lds[4] = A.mb_off >= 0 ? 1 : 0;
+        g->last_lds[5] = A.tri_prefix;
+        g->last_lds[6] = (int32_t)lds;
+        g->last_lds[7] = A.sah;
     }
     const void* fn = (const void*)kf;
     HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -184,7 +184,8 @@ class DeviceWorld:
 
     def kernel_variant(self) -> dict:
         """The render-kernel variant of the last render (LDS mode, leaf kinds, texture kinds, tree, and the
-        kernel's exact template name)."""
+        kernel's exact template name), and where that launch put its tables: `shade_lds`, `tex_lds`, `proof_lds`,
+        `gen_lds` (1 in LDS, 0 in HBM / L2), `mailbox`, `tri_prefix`, `lds_bytes`, `sah`."""
         m, lk, tx, tr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         check(lib().rtw_world_kernel(self._h, C.byref(m), C.byref(lk), C.byref(tx), C.byref(tr)))
         name = C.create_string_buffer(64)
@@ -193,6 +194,12 @@ class DeviceWorld:
                "tree": ("reference", "sah")[tr.value] if tr.value >= 0 else None,
                # the exact template name (GEN included), as rocprofv3's Kernel_Name holds it
                "name": name.value.decode()}
+        if hasattr(lib(), "rtw_world_last_launch_lds"):  # (absent from an older experiment build, A/B runs)
+            t = (C.c_int32 * 8)()
+            check(lib().rtw_world_last_launch_lds(self._h, t))
+            # where the launch put its tables (1 in LDS, 0 in HBM / L2), rtw_world_last_launch_lds
+            out.update(zip(("shade_lds", "tex_lds", "proof_lds", "gen_lds", "mailbox", "tri_prefix", "lds_bytes", "sah"),
+                           (int(v) for v in t)))
         out.update(self._lists())  # the primary rays' leaf lists of the last frame
         return out
 

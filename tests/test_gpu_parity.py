@@ -10,6 +10,7 @@ import pytest
 import raytracinginaweekend_amd as R
 from oracle import pyoracle as O
 from tests.parity import assert_bit_identical
+from tests.variant_worlds import soup_world as _soup_world, sphere_cloud as _sphere_cloud
 
 pytestmark = pytest.mark.gpu
 
@@ -713,22 +714,6 @@ def _ok_metal(wb, tex: int, fuzz: float) -> int:
     return r
 
 
-def _soup_world(n_tri: int, seed: int = 5):
-    """A random triangle soup over a ground sphere (mesh worlds of any size)."""
-    rng = np.random.default_rng(seed)
-    wb = R.WorldBuilder()
-    mats = [wb.material_lambert_solid((0.7, 0.3, 0.2)), wb.material_metal_solid((0.8, 0.8, 0.8), 0.2)]
-    g = wb.new_group()
-    g.add(wb.new_obj_sphere(100.0, mats[0]).translate((0.0, -100.0, 0.0)))
-    c = rng.uniform((-2.0, 0.2, -2.0), (2.0, 2.2, 2.0), (n_tri, 1, 3))
-    v = (c + rng.uniform(-0.25, 0.25, (n_tri, 3, 3))).astype(np.float32)
-    tris = np.concatenate([v.reshape(n_tri, 9), np.tile(np.float32([0, 1, 0]), (n_tri, 3)),
-                           np.zeros((n_tri, 6), np.float32)], 1).astype(np.float32)
-    g.add(wb.new_mesh(tris, mats[1]))
-    cam = R.Camera.build().vertical_fov(50.0, 9.0 / 16.0).position((0.0, 1.5, 6.0)).look_at((0, 1, 0), (0, 1, 0)).build()
-    return g.build().finish(wb, R.BackgroundColor.sky(), cam)
-
-
 @pytest.mark.parametrize("n_tri,mode2", [(300, True), (1100, True), (2000, False)])
 def test_triangle_records_lds_fallback(n_tri, mode2):
     """LDS mode 2 holds the triangle records component-major at the world's own stride (its triangle
@@ -749,21 +734,6 @@ def test_triangle_records_lds_fallback(n_tri, mode2):
     size = R.Size2i(40, 24)
     assert_bit_identical(R.render(size, 1, 4, 50, world, seed=13), O.render(world, R.render_params(size, 4, 50, seed=13)),
                          f"soup {n_tri}")
-
-
-def _sphere_cloud(n: int, seed: int = 3):
-    """n small plain spheres in a slab over a ground sphere (n - 1 spheres + ground = n leaves)."""
-    rng = np.random.default_rng(seed)
-    wb = R.WorldBuilder()
-    mats = [wb.material_lambert_solid((0.7, 0.3, 0.2)), wb.material_metal_solid((0.8, 0.8, 0.8), 0.1),
-            wb.material_dielectric(1.5)]
-    g = wb.new_group()
-    g.add(wb.new_obj_sphere(1000.0, mats[0]).translate((0.0, -1000.0, 0.0)))
-    c = rng.uniform((-8.0, 0.05, -8.0), (8.0, 3.0, 8.0), (n - 1, 3)).astype(np.float32)
-    for i in range(n - 1):
-        g.add(wb.new_obj_sphere(0.04, mats[i % 3]).translate(tuple(float(x) for x in c[i])))
-    cam = R.Camera.build().vertical_fov(50.0, 9.0 / 16.0).position((0.0, 2.0, 10.0)).look_at((0, 1, 0), (0, 1, 0)).build()
-    return g.build().finish(wb, R.BackgroundColor.sky(), cam)
 
 
 @pytest.mark.parametrize("n,folded", [(16384, True), (16385, False)])
