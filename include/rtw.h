@@ -303,13 +303,21 @@ RTW_API int rtw_world_last_launch_lds(rtw_gpu_world* gw, int32_t out[8]);
  * first render.  The leaf-list kernel's single-sample variants (WP false) carry a seventh place, their camera
  * batch; its whole-pixel variants keep six:
  * "render_kernel_pl<false, 1, 0, 0, false, false, true>"; RTW_CAMERA_BATCH=0 selects the "false" kernel.
+ * The solid-texture batch kernel that also shades the camera hit in the fill carries an eighth place, put
+ * before the batch's: "render_kernel_pl<false, 1, 0, 0, false, false, true, true>"; RTW_FIRST_BOUNCE=0
+ * selects the seven-place batch kernel.
  * RTW_ERR_INVALID_ARGUMENT if cap is too small.  Diagnostics only (bench.py matches PMC rows by it). */
 RTW_API int rtw_world_kernel_name(rtw_gpu_world* gw, char* buf, int cap);
 /* Tests: the camera batch's counters on `device`, summed over the render launches since the last reset:
- * out3 = fills, records stored valid, records picked up valid.  The last two are equal, and equal to the
- * samples rendered, when every work item was traced exactly once; kernels without the batch add nothing.
- * Synchronous; reset != 0 zeroes them. */
+ * out3 = fills, samples stored, samples picked.  "Stored" is a valid sample prepared by a fill; "picked" is a
+ * sample that left the fill's custody: a record handed to a lane, or a sample the fill finished itself (first
+ * bounce).  The last two are equal, and equal to the samples rendered, when every work item was traced exactly
+ * once; kernels without the batch add nothing.  Synchronous; reset != 0 zeroes them. */
 RTW_API int rtw_debug_park_counts(int device, unsigned long long* out3, int reset);
+/* Tests: what the fills of the first-bounce kernel did with their samples, summed like the counters above:
+ * out3 = samples finished in the fill (no record), bounce records parked, unsolved records parked.  Their sum
+ * is "stored"; kernels without the first bounce add nothing.  Synchronous; reset != 0 zeroes them. */
+RTW_API int rtw_debug_fill_counts(int device, unsigned long long* out3, int reset);
 /* The shape of this world's last frame (rtw_render_device / rtw_render on it): render-kernel launches,
  * whether the work items were whole pixels (1: samples summed in registers, no colour buffer, DESIGN.md
  * 5.5b; 0: single samples through the colour buffer), and the dynamic-fetch threshold it ran with (the

@@ -300,6 +300,7 @@ _SIGS = {
     "rtw_world_last_launch_lds": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "rtw_world_kernel_name": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "rtw_debug_park_counts": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.c_int]),
+    "rtw_debug_fill_counts": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.c_int]),
     "rtw_world_last_frame": (C.c_int, [_P] + [C.POINTER(C.c_int)] * 3),
     "rtw_world_last_frame_lists": (C.c_int, [_P] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_double)]),
     "rtw_world_primary_lists": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),

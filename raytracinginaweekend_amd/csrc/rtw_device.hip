@@ -1500,20 +1500,27 @@ __device__ __forceinline__ Ray camera_ray(const rtw_camera& c, rtw_xoro& rng, fl
 // (sums 8..11, read by rtw_debug_phase_extra: 8 the camera rays' share of phase 2 -- the leaf-list scan, and the
 // whole set-up of an iteration in which no scattered ray starts; 10, 11 the refill rounds that handed out an
 // item and the PH_PIXEL lanes they found)
-#define RTW_PT_SUMS 12
+#define RTW_PT_SUMS 20
+// (sums 12..18, read by rtw_debug_phase_skip: the main loop's shade passes split by whether the iteration skipped
+// the walk (tmin = 65, the camera-only passes): 12, 13 passes and lanes of the skipping iterations, 14, 15 of the
+// others, 16..18 the cycles of phases 4, 6 and 7 inside the skipping iterations -- part of sums 4, 6, 7 too)
 __device__ unsigned long long rtw_phase_cycles[RTW_PT_SUMS];
-__device__ __forceinline__ unsigned long long* pt_slot() {
-    __shared__ unsigned long long s[(RTW_BLOCK / 64) * (RTW_PT_SUMS + 2)];
-    return s + (threadIdx.x >> 6) * (RTW_PT_SUMS + 2);
+__device__ __forceinline__ unsigned long long* pt_slot() {  // per wave: the sums, the last stamp, the phase, the skip flag
+    __shared__ unsigned long long s[(RTW_BLOCK / 64) * (RTW_PT_SUMS + 3)];
+    return s + (threadIdx.x >> 6) * (RTW_PT_SUMS + 3);
 }
-#define RTW_PT_DECL do { unsigned long long* s_ = pt_slot(); if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < RTW_PT_SUMS; ++k_) s_[k_] = 0; s_[RTW_PT_SUMS] = clock64(); s_[RTW_PT_SUMS + 1] = 0; } } while (0);
-#define RTW_PT(k) do { if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) { unsigned long long* s_ = pt_slot(); const unsigned long long now_ = clock64(); s_[s_[RTW_PT_SUMS + 1]] += now_ - s_[RTW_PT_SUMS]; s_[RTW_PT_SUMS] = now_; s_[RTW_PT_SUMS + 1] = (k); } } while (0)
+#define RTW_PT_DECL do { unsigned long long* s_ = pt_slot(); if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < RTW_PT_SUMS; ++k_) s_[k_] = 0; s_[RTW_PT_SUMS] = clock64(); s_[RTW_PT_SUMS + 1] = 0; s_[RTW_PT_SUMS + 2] = 0; } } while (0);
+#define RTW_PT(k) do { if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) { unsigned long long* s_ = pt_slot(); const unsigned long long now_ = clock64(); const unsigned long long c_ = s_[RTW_PT_SUMS + 1], d_ = now_ - s_[RTW_PT_SUMS]; s_[c_] += d_; if (s_[RTW_PT_SUMS + 2] && (c_ == 4 || c_ == 6 || c_ == 7)) s_[c_ == 4 ? 16 : c_ == 6 ? 17 : 18] += d_; s_[RTW_PT_SUMS] = now_; s_[RTW_PT_SUMS + 1] = (k); } } while (0)
 #define RTW_PT_ROUND(leader, lanes) do { if ((int)(threadIdx.x & 63) == (leader)) { unsigned long long* s_ = pt_slot(); s_[10] += 1; s_[11] += (lanes); } } while (0)
+#define RTW_PT_SKIP(on) do { if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) pt_slot()[RTW_PT_SUMS + 2] = (on) ? 1 : 0; } while (0)
+#define RTW_PT_SHADE(mask) do { const unsigned long long m_ = (mask); if (m_ && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) { unsigned long long* s_ = pt_slot(); const int b_ = s_[RTW_PT_SUMS + 2] ? 12 : 14; s_[b_] += 1; s_[b_ + 1] += (unsigned long long)__popcll(m_); } } while (0)
 #define RTW_PT_FLUSH do { RTW_PT(0); if ((threadIdx.x & 63) == 0) for (int k_ = 0; k_ < RTW_PT_SUMS; ++k_) atomicAdd(&rtw_phase_cycles[k_], pt_slot()[k_]); } while (0)
 #else
 #define RTW_PT_DECL
 #define RTW_PT(k) do { } while (0)
 #define RTW_PT_ROUND(leader, lanes) do { } while (0)
+#define RTW_PT_SKIP(on) do { } while (0)
+#define RTW_PT_SHADE(mask) do { } while (0)
 #define RTW_PT_FLUSH do { } while (0)
 #endif
 
@@ -1676,12 +1683,21 @@ __device__ __forceinline__ ShadeOut shade(const DWorld* __restrict__ wp, int32_t
 // atomics) and added here once per block at its end (as one global atomic per post, the counters cost
 // suzanne's 8-way shares 13 %: every block's drain contended on three addresses)
 __device__ unsigned long long rtw_drain_counts[3];
-// the camera batch's traffic (rtw_debug_park_counts; tests): fills, records stored valid, records picked up
-// valid -- the last two are equal, and equal to the launch's samples, when every item is traced exactly once
+// the camera batch's traffic (rtw_debug_park_counts; tests): fills, samples stored, samples picked.  "Stored" is
+// a valid sample prepared by a fill; "picked" is a sample that left the fill's custody: a record handed to a
+// lane, or a sample the fill finished itself (FB).  The last two are equal, and equal to the launch's samples,
+// when every item is traced exactly once
 __device__ unsigned long long rtw_park_counts[3];
+// ... and what the first-bounce fills did with their samples (rtw_debug_fill_counts; tests): samples finished in
+// the fill, bounce records parked, unsolved records parked -- their sum is "stored"
+__device__ unsigned long long rtw_fill_counts[3];
 // a parked record: 5 groups of 16 bytes (origin + time; direction + te; inv + fast | phase << 8 | valid << 16;
 // the RNG state after the camera's draws; found, slot, sample)
 #define RTW_PARK_GROUPS 5
+// the first-bounce kernel's record, 7 groups (25 dwords): (origin + time; direction + te; inv + fast | phase << 8;
+// the RNG state; found, slot, sample, depth; att + pdot; acc) -- a bounce ray ready to trace, or an unsolved
+// camera ray with att = 1, acc = 0, depth = max_depth.  Only parking lanes write one: every record is valid
+#define RTW_PARK_GROUPS_FB 7
 
 #ifdef RTW_WAVE_TIMING  // experiment builds: per-wave start / end / queue-empty wall clocks of the last launch
 __device__ unsigned long long rtw_wave_times[3 * 8192];
@@ -2226,16 +2242,76 @@ __device__ __forceinline__ void sah_take(Trav& T, float t, int leaf) {
     T.found = same ? T.found : leaf;
 }
 
+// Two steps of render_body that the main loop and the first-bounce fill both run, on T and on the fill's F.  They
+// are macros, expanded where render_body's A, w, sah, st, STATS and LK are in scope, and not functions: as
+// inlined functions they moved the SGPR spills of most render kernels (make resources), as text every kernel that
+// had these statements in its loop compiles to the code it had.
+// RTW_RAY_START: the start of a ray (step 2, and the bounce rays the fill parks): the reciprocals (declares
+// `rp`), the sign bits, the root of the tree it walks and an empty result.
+#define RTW_RAY_START(T, rp)                                                                                          \
+    const RayPre rp = ray_pre((T).ray, A.mk_world != 0);                                                              \
+    (T).inv = rp.inv;                                                                                                 \
+    (T).fast = (rp.fast ? 8 : 0) | ((T).ray.d.x > 0.0f ? 1 : 0) | ((T).ray.d.y > 0.0f ? 2 : 0) | ((T).ray.d.z > 0.0f ? 4 : 0); \
+    (T).node = w.root;                                                                                                \
+    if (sah) { /* the SAH walk needs the exact fast division; other rays take the reference tree */                  \
+        if (rp.fast) {                                                                                                \
+            (T).node = LK == LK_SPHERES ? w.sah_root_c2 : w.sah_root;                                                 \
+            (T).fast |= RTW_TF_SAH;                                                                                   \
+        } else {                                                                                                      \
+            (T).phase = PH_REF;                                                                                       \
+        }                                                                                                             \
+    }                                                                                                                 \
+    (T).sp = 0;                                                                                                       \
+    (T).te = F32_INF;                                                                                                 \
+    (T).found = -1;
+// RTW_SAH_PROOF (§5.5): the SAH walk's closest leaf L (no tie) is the reference's answer when the reference DFS
+// reaches L: the reference's internal boxes are nested (checked at upload) and hit_cond is monotone under box
+// inclusion and in te, so L's parent box passing hit_cond with te = succ(t) proves it.  A miss is a miss for the
+// reference too.  Declares `ok`; the ray leaves with te = the closest t and without RTW_TF_SAH | RTW_TF_TIE.
+// RTW_REF_RESTART: a ray the proof fails is traced again on the reference tree.
+#ifdef RTW_SAH_AUDIT_NO_TIE  // audit builds only: shows that the tie test decides images
+#define RTW_PROOF_TIE(ok) ok = true;
+#else
+#define RTW_PROOF_TIE(ok)
+#endif
+#ifndef RTW_SAH_AUDIT_NO_BOX  // audit builds only: shows that the leaf-box proof decides images
+#define RTW_PROOF_BOX(T, ok) ok = ok && box_hit_cond_fast(ba, bb, (T).ray, RayPre{(T).inv, true}, 0.001f, (T).te);
+#else
+#define RTW_PROOF_BOX(T, ok) (void)ba, (void)bb;
+#endif
+#define RTW_SAH_PROOF(T, ok)                                                                                          \
+    bool ok = ((T).fast & RTW_TF_TIE) == 0;                                                                           \
+    RTW_PROOF_TIE(ok)                                                                                                 \
+    if ((T).found >= 0) {                                                                                             \
+        if (STATS) st.c[ST_NODES]++; /* the leaf-box proof reads one 32-B box record */                               \
+        const float4 ba = A.sh_box >= 0 ? smem[A.sh_box + 2 * (T).found] : w.leaf_box[2 * (T).found];                 \
+        const float4 bb = A.sh_box >= 0 ? smem[A.sh_box + 2 * (T).found + 1] : w.leaf_box[2 * (T).found + 1];         \
+        RTW_PROOF_BOX(T, ok)                                                                                          \
+        (T).te = __int_as_float(__float_as_int((T).te) - 1); /* the closest t */                                      \
+    }                                                                                                                 \
+    (T).fast &= ~(RTW_TF_SAH | RTW_TF_TIE);
+#define RTW_REF_RESTART(T)                                                                                            \
+    (T).phase = PH_REF;                                                                                               \
+    (T).node = w.root;                                                                                                \
+    (T).sp = 0;                                                                                                       \
+    (T).te = F32_INF;                                                                                                 \
+    (T).found = -1;
+
 // PL (render_kernel_pl): camera rays of tiles that have a leaf list (rtw_beam.h) find their closest hit by
 // testing the listed leaves instead of walking the SAH tree.  Plain-sphere SAH worlds in LDS mode 1 only; every
 // other variant compiles none of it.
 // CB (render_kernel_pl<.., true>): the wave prepares the camera rays of up to 64 consecutive items of its reserve
 // with all its lanes at once (stream, jitter, camera ray, reciprocals, the tile's list) and parks them in A.park;
 // a lane that finished a sample only picks a record up.  Single-sample items, no tuner, no counting.
-template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool PL = false, bool CB = false>
+// FB (render_kernel_pl<.., true, true>, the TX_SOLID batch kernel): the fill also takes the first bounce of the
+// camera rays its lists settle -- a miss, or a hit that passes the leaf-box proof without a tie.  It shades them
+// with all its lanes, stores the samples that end there and parks the others' scattered rays ready to trace.
+template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool PL = false, bool CB = false, bool FB = false>
 __device__ __forceinline__ void render_body(const KArgs& A) {
     static_assert(!PL || (LDS == 1 && LK == LK_SPHERES && !GEN), "leaf lists: plain-sphere worlds, LDS mode 1");
     static_assert(!CB || (PL && !WP && !STATS), "camera batch: the leaf-list kernel's single-sample variants");
+    static_assert(!FB || CB, "first bounce: a step of the camera batch's fill");
+    constexpr int PARK_GROUPS = FB ? RTW_PARK_GROUPS_FB : RTW_PARK_GROUPS;
     constexpr bool LDS_SCENE = LDS >= 1;
     // LDS: [scene: nodes (2 float4 each), leaf records (1 float4 each), cull constants (1 float2
     // per node)] [stack: depth x BLOCK]
@@ -2302,7 +2378,9 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
         LDS_SCENE && LK >= LK_PLAIN ? A.sh_rect : -1,
         LK == LK_TRIS ? A.tri_prefix : 0, A.tri_prefix_mat, A.tri_prefix_w};
     // the shading tables' offsets in VGPRs: as SGPRs they are live across the bounce loop and spill
-    asm volatile("" : "+v"(stabs.li), "+v"(stabs.mat), "+v"(stabs.tex0), "+v"(stabs.fast));
+    // (not in the first-bounce kernel: beside its fill's shade call the four VGPRs went to scratch, 20 B per lane,
+    // and as spilled SGPRs they cost lanes of the spill registers only)
+    if constexpr (!FB) asm volatile("" : "+v"(stabs.li), "+v"(stabs.mat), "+v"(stabs.tex0), "+v"(stabs.fast));
     if (LK == LK_TRIS) asm volatile("" : "+v"(stabs.pre), "+v"(stabs.pre_mat), "+v"(stabs.pre_w));
     Stats st;
     if (STATS)
@@ -2367,6 +2445,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
     uint32_t qfail = 0;           // consecutive queues found empty: RTW_QUEUES of them end the launch
     uint32_t p_next = 0, p_count = 0;                   // (CB) the park's records [p_next, p_count) wait for a lane
     uint32_t pk_fills = 0, pk_stored = 0, pk_picked = 0;  // (CB) rtw_park_counts, per wave
+    uint32_t fc_fin = 0, fc_bounce = 0, fc_unsolved = 0;   // (FB) rtw_fill_counts, per wave
     unsigned long long pf_b = 0;  // the prefetched batch's base, in lane pf_lane (its atomic's result)
     uint64_t pf_size = 0;         // its size; 0: none in flight
     int pf_lane = 0;
@@ -2445,6 +2524,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                     w_next += left;
                     if (left) RTW_PT_ROUND(leader, (uint64_t)__popcll(m));
                     bool valid = false;
+                    bool parks = false, shaded = false;  // (FB) the lane parks a record; ... of a bounce ray
                     if ((uint32_t)lane < left) {  // every lane, whatever its phase: item first + lane on temporaries
                         const uint64_t loc = first + (uint32_t)lane;
                         const uint64_t item = ((loc / RTW_QGRAN) * RTW_QUEUES + wq) * RTW_QGRAN + loc % RTW_QGRAN;
@@ -2475,7 +2555,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                             f_slot = c;
                             f_sample = big ? A.s_begin + ck * A.chunk : A.s_split + ck;  // (chunk = 1)
                         }
-                        float4* P = A.park + ((size_t)(blockIdx.x * (RTW_BLOCK / 64) + (threadIdx.x >> 6)) * RTW_PARK_GROUPS) * 64 + lane;
+                        float4* P = A.park + ((size_t)(blockIdx.x * (RTW_BLOCK / 64) + (threadIdx.x >> 6)) * PARK_GROUPS) * 64 + lane;
                         if (valid) {
                             RTW_PT(5);
                             // rendering.rs:174-176: jitter (x then y), then Camera::ray (start_sample's expressions)
@@ -2511,13 +2591,79 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                                 }
                             }
                             RTW_PT(1);
+                            if constexpr (!FB) {
                             P[0 * 64] = make_float4(F.ray.o.x, F.ray.o.y, F.ray.o.z, F.ray.time);
                             P[1 * 64] = make_float4(F.ray.d.x, F.ray.d.y, F.ray.d.z, F.te);
                             P[2 * 64] = make_float4(rp.inv.x, rp.inv.y, rp.inv.z, __int_as_float(F.fast | (F.phase << 8) | (1 << 16)));
                             P[3 * 64] = make_float4(__int_as_float((int)(uint32_t)f_rng.s0), __int_as_float((int)(uint32_t)(f_rng.s0 >> 32)),
                                                     __int_as_float((int)(uint32_t)f_rng.s1), __int_as_float((int)(uint32_t)(f_rng.s1 >> 32)));
                             P[4 * 64] = make_float4(__int_as_float(F.found), __int_as_float((int)f_slot), __int_as_float((int)f_sample), 0.0f);
-                        } else {
+                            } else {
+                                // (FB) the first bounce of the settled camera rays: the main loop's proof step and
+                                // its shade call, here with every lane of the fill.  The parking lanes' records are
+                                // compacted: the unsolved rays' first, written before the shade call so that none
+                                // of their state is live across it, then the bounce rays'
+                                const float f_pdot = dot(v3(0.0f, 1.0f, 0.0f), F.ray.d);  // background_color.rs:13
+                                auto put = [&](uint32_t k, const V3& at, const V3& ac, int32_t dp) {  // record k of the park
+                                    float4* R = P - lane + k;
+                                    R[0 * 64] = make_float4(F.ray.o.x, F.ray.o.y, F.ray.o.z, F.ray.time);
+                                    R[1 * 64] = make_float4(F.ray.d.x, F.ray.d.y, F.ray.d.z, F.te);
+                                    R[2 * 64] = make_float4(F.inv.x, F.inv.y, F.inv.z, __int_as_float(F.fast | (F.phase << 8)));
+                                    R[3 * 64] = make_float4(__int_as_float((int)(uint32_t)f_rng.s0), __int_as_float((int)(uint32_t)(f_rng.s0 >> 32)),
+                                                            __int_as_float((int)(uint32_t)f_rng.s1), __int_as_float((int)(uint32_t)(f_rng.s1 >> 32)));
+                                    R[4 * 64] = make_float4(__int_as_float(F.found), __int_as_float((int)f_slot), __int_as_float((int)f_sample),
+                                                            __int_as_float(dp));
+                                    R[5 * 64] = make_float4(at.x, at.y, at.z, f_pdot);
+                                    R[6 * 64] = make_float4(ac.x, ac.y, ac.z, 0.0f);
+                                };
+                                F.inv = rp.inv;
+                                bool settled = false;
+                                if (F.phase == PH_SHADE && (F.fast & RTW_TF_TIE) == 0) {  // (a tie waits for the main loop)
+                                    RTW_SAH_PROOF(F, ok)
+                                    settled = ok;
+                                    if (!ok) {
+                                        RTW_REF_RESTART(F)
+                                    }
+                                }
+                                const unsigned long long um = __ballot(!settled);  // (over the fill's valid lanes)
+                                if (!settled) {
+                                    const unsigned long long below = (lane == 0) ? 0ull : (um & (~0ull >> (64 - lane)));
+                                    put((uint32_t)__popcll(below), v3(1.0f, 1.0f, 1.0f), v3(0.0f, 0.0f, 0.0f), A.max_depth);
+                                    parks = true;
+                                }
+                                if (um != __ballot(1)) {  // (uniform over those lanes) else: no lane has a ray to shade
+                                    if (settled) {
+                                        RTW_PT(4);
+                                        Path Q;
+                                        Q.ray = F.ray;
+                                        Q.att = v3(1.0f, 1.0f, 1.0f);
+                                        Q.acc = v3(0.0f, 0.0f, 0.0f);
+                                        Q.depth = A.max_depth;
+                                        Q.rng = f_rng;
+                                        const ShadeOut so = shade<false, TX>(A.wdev, A.mode, Q, F.found, F.te, f_pdot, stabs);
+                                        if (so.done) {  // step 4's store (its bounce count is below 4: no slot cost)
+                                            RTW_PT(7);
+                                            float* o = A.colors + ((uint64_t)(f_sample - A.s_begin) * A.total + f_slot) * 3;
+                                            o[0] = so.color.x;
+                                            o[1] = so.color.y;
+                                            o[2] = so.color.z;
+                                        } else {  // step 2's start of the scattered ray
+                                            RTW_PT(2);
+                                            F.ray = so.p.ray;
+                                            f_rng = so.p.rng;
+                                            F.phase = PH_TRACE;
+                                            RTW_RAY_START(F, rb)
+                                            (void)rb;
+                                            const unsigned long long bm = __ballot(1);
+                                            const unsigned long long below = (lane == 0) ? 0ull : (bm & (~0ull >> (64 - lane)));
+                                            put((uint32_t)__popcll(um) + (uint32_t)__popcll(below), so.p.att, so.p.acc, so.p.depth);
+                                            parks = shaded = true;
+                                        }
+                                        RTW_PT(1);
+                                    }
+                                }
+                            }
+                        } else if constexpr (!FB) {
                             P[2 * 64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // an invalid record: consumed like any other
                         }
                     }
@@ -2526,6 +2672,15 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                         pk_stored += (uint32_t)__popcll(__ballot(valid));
                         p_next = 0;
                         p_count = left;
+                        if constexpr (FB) {  // the records parked; a sample the fill finished has left its custody
+                            const uint32_t n_fin = (uint32_t)__popcll(__ballot(valid && !parks));
+                            const uint32_t n_bounce = (uint32_t)__popcll(__ballot(shaded));
+                            p_count = (uint32_t)__popcll(__ballot(parks));
+                            pk_picked += n_fin;
+                            fc_fin += n_fin;
+                            fc_bounce += n_bounce;
+                            fc_unsolved += p_count - n_bounce;
+                        }
                         // the records are written by the lanes of this wave that read them: wavefront scope
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2537,7 +2692,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                     } else if (took) {
                         qfail = 0;
                     }
-                    if (!left) continue;
+                    if (!left || (FB && p_count == 0)) continue;  // (FB: a fill whose samples all finished parks nothing)
                 }
                 // the pick-up: the PH_PIXEL lanes take the next records in lane order
                 const uint32_t avail = p_count - p_next;
@@ -2546,10 +2701,10 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                     const unsigned long long below = (lane == 0) ? 0ull : (m & (~0ull >> (64 - lane)));
                     const uint32_t r = (uint32_t)__popcll(below);
                     if (r < avail) {
-                        const float4* P = A.park + ((size_t)(blockIdx.x * (RTW_BLOCK / 64) + (threadIdx.x >> 6)) * RTW_PARK_GROUPS) * 64 + (p_next + r);
+                        const float4* P = A.park + ((size_t)(blockIdx.x * (RTW_BLOCK / 64) + (threadIdx.x >> 6)) * PARK_GROUPS) * 64 + (p_next + r);
                         const float4 q2 = P[2 * 64];
                         const int32_t bits = __float_as_int(q2.w);
-                        if (bits >> 16) {
+                        if (FB || (bits >> 16)) {  // (FB: only parking lanes wrote a record, each is valid)
                             const float4 q0 = P[0 * 64], q1 = P[1 * 64], q3 = P[3 * 64], q4 = P[4 * 64];
                             T.ray.o = v3(q0.x, q0.y, q0.z);
                             T.ray.time = q0.w;
@@ -2565,10 +2720,18 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                             sample = (uint32_t)__float_as_int(q4.z);
                             T.node = (T.fast & RTW_TF_SAH) ? w.sah_root_c2 : w.root;
                             T.sp = 0;
+                            if constexpr (FB) {  // the path's state as the fill left it (a bounce ray, or a camera ray)
+                                const float4 q5 = P[5 * 64], q6 = P[6 * 64];
+                                depth = __float_as_int(q4.w);
+                                att = v3(q5.x, q5.y, q5.z);
+                                pdot = q5.w;
+                                acc = v3(q6.x, q6.y, q6.z);
+                            } else {
                             pdot = dot(v3(0.0f, 1.0f, 0.0f), T.ray.d);  // background_color.rs:13 on the primary ray
                             att = v3(1.0f, 1.0f, 1.0f);
                             acc = v3(0.0f, 0.0f, 0.0f);
                             depth = A.max_depth;
+                            }
                             got = true;
                         }
                     }
@@ -2733,21 +2896,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
 #endif
         if (fresh) {
             fresh = false;
-            const RayPre rp = ray_pre(T.ray, A.mk_world != 0);
-            T.inv = rp.inv;
-            T.fast = (rp.fast ? 8 : 0) | (T.ray.d.x > 0.0f ? 1 : 0) | (T.ray.d.y > 0.0f ? 2 : 0) | (T.ray.d.z > 0.0f ? 4 : 0);
-            T.node = w.root;
-            if (sah) {  // the SAH walk needs the exact fast division; other rays take the reference tree
-                if (rp.fast) {
-                    T.node = LK == LK_SPHERES ? w.sah_root_c2 : w.sah_root;
-                    T.fast |= RTW_TF_SAH;
-                } else {
-                    T.phase = PH_REF;
-                }
-            }
-            T.sp = 0;
-            T.te = F32_INF;
-            T.found = -1;
+            RTW_RAY_START(T, rp)
             if (STATS) st.c[ST_RAYS]++;
             if constexpr (PL && !CB) {  // (CB: the fill has resolved the camera rays)
                 // a camera ray of a listed tile: the tile's leaves through the walk's own sphere test and take(),
@@ -2790,6 +2939,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
             // the lanes go straight to the proof and the one shade call; with fewer they wait through one round
             int32_t tmin = __builtin_amdgcn_readfirstlane(trace_min);
             if (PL && (int32_t)__popcll(__ballot(T.phase == PH_SHADE)) >= A.pl_shade_min) tmin = 65;
+            RTW_PT_SKIP(tmin == 65);
             T = traverse<STATS, LDS, LK, true, TM_SAH>(A.wdev, stabs, T, tmin, A.node_count,
                                                        A.leaf_count, A.rect_count, A.tri_prefix, A.tri_stride, stack_off,
                                                        STATS ? A.stats + ST_COUNT : nullptr, dry_coop ? A.coop_max : -1);
@@ -2893,34 +3043,12 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
                 st.c[ST_T_TRI] += T.n_box_tri >> 16;
                 T.n_nodes = T.n_sph_rect = T.n_box_tri = 0;
             }
-            // §5.5: the SAH walk's closest leaf L (no tie) is the reference's answer when the
-            // reference DFS reaches L: the reference's internal boxes are nested (checked at upload)
-            // and hit_cond is monotone under box inclusion and in te, so L's parent box passing
-            // hit_cond with te = succ(t) proves it.  A miss is a miss for the reference too.
-            // Otherwise the ray is traced again on the reference tree.
+            // §5.5: the leaf-box proof of the walk's answer (sah_proof); a ray it does not prove is traced again
+            // on the reference tree
             if (T.phase == PH_SHADE && (T.fast & RTW_TF_SAH)) {
-                bool ok = (T.fast & RTW_TF_TIE) == 0;
-#ifdef RTW_SAH_AUDIT_NO_TIE  // audit builds only: shows that the tie test decides images
-                ok = true;
-#endif
-                if (T.found >= 0) {
-                    if (STATS) st.c[ST_NODES]++;  // the leaf-box proof reads one 32-B box record
-                    const float4 ba = A.sh_box >= 0 ? smem[A.sh_box + 2 * T.found] : w.leaf_box[2 * T.found];
-                    const float4 bb = A.sh_box >= 0 ? smem[A.sh_box + 2 * T.found + 1] : w.leaf_box[2 * T.found + 1];
-#ifndef RTW_SAH_AUDIT_NO_BOX  // audit builds only: shows that the leaf-box proof decides images
-                    ok = ok && box_hit_cond_fast(ba, bb, T.ray, RayPre{T.inv, true}, 0.001f, T.te);
-#else
-                    (void)ba, (void)bb;
-#endif
-                    T.te = __int_as_float(__float_as_int(T.te) - 1);  // the closest t
-                }
-                T.fast &= ~(RTW_TF_SAH | RTW_TF_TIE);
+                RTW_SAH_PROOF(T, ok)
                 if (!ok) {
-                    T.phase = PH_REF;
-                    T.node = w.root;
-                    T.sp = 0;
-                    T.te = F32_INF;
-                    T.found = -1;
+                    RTW_REF_RESTART(T)
                 }
             }
 #ifdef RTW_WAVE_TIMING
@@ -2958,6 +3086,7 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
 
         // 4. shade the lanes whose traversal finished (rendering.rs:19-71)
         RTW_PT(4);
+        RTW_PT_SHADE(__ballot(T.phase == PH_SHADE));
         if (STATS) {
             const unsigned long long sm = __ballot(T.phase == PH_SHADE);
             if (sm && lane == __ffsll((long long)__ballot(1)) - 1) {
@@ -3068,6 +3197,9 @@ __device__ __forceinline__ void render_body(const KArgs& A) {
     if constexpr (CB) {  // the wave's counts, one atomic instruction per wave
         if (lane < 3) atomicAdd(&rtw_park_counts[lane], (unsigned long long)(lane == 0 ? pk_fills : lane == 1 ? pk_stored : pk_picked));
     }
+    if constexpr (FB) {
+        if (lane < 3) atomicAdd(&rtw_fill_counts[lane], (unsigned long long)(lane == 0 ? fc_fin : lane == 1 ? fc_bounce : fc_unsolved));
+    }
     RTW_PT_FLUSH;
 #ifdef RTW_WAVE_TIMING
     {
@@ -3122,6 +3254,13 @@ template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool CB>
 __global__ __launch_bounds__(RTW_BLOCK, RTW_MIN_WAVES_PER_SIMD) void render_kernel_pl(KArgs A) {
     static_assert(!STATS && !WP, "seven places: the single-sample product kernels");
     render_body<STATS, LDS, LK, TX, GEN, WP, true, CB>(A);
+}
+// ... and the batch kernel with the first bounce in its fill (render_body's FB) an eighth, put before CB: the
+// names of both batch kernels end in ", true>".
+template <bool STATS, int LDS, int LK, int TX, bool GEN, bool WP, bool FB, bool CB>
+__global__ __launch_bounds__(RTW_BLOCK, RTW_MIN_WAVES_PER_SIMD) void render_kernel_pl(KArgs A) {
+    static_assert(!STATS && !WP && FB && CB && TX == TX_SOLID, "eight places: the solid-texture batch kernel's first bounce");
+    render_body<STATS, LDS, LK, TX, GEN, WP, true, CB, FB>(A);
 }
 
 // The list builder: one tile per 64-thread group, every leaf tested by rtw_beam.h's rule (the host builder's
@@ -4461,6 +4600,7 @@ struct rtw_gpu_world {
     double pl_build_ms = 0.0;        // the builder kernel's time (device events)
     int32_t last_pl = 0;             // the last render took render_kernel_pl
     int32_t last_cb = 0;             // ... its camera-batch variant
+    int32_t last_fb = 0;             // ... with the first bounce in the fill
     float4* park = nullptr;          // the camera batch's records (launch_render grows it)
     size_t park_bytes = 0;
     int32_t last_lists[3] = {0, 0, 0};  // pl_info of the last frame (zeros: the frame used no lists)
@@ -4511,7 +4651,8 @@ extern "C" RTW_API int rtw_debug_drain_counts(int device, unsigned long long* ou
     return RTW_OK;
 }
 
-// tests: the camera batch's counters (rtw_park_counts: fills, records stored valid, records picked up valid),
+// tests: the camera batch's counters (rtw_park_counts: fills, samples stored, samples picked -- handed to a lane or
+// finished by the fill),
 // summed over the launches since the last reset
 extern "C" RTW_API int rtw_debug_park_counts(int device, unsigned long long* out3, int reset) {
     if (!out3) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
@@ -4521,6 +4662,20 @@ extern "C" RTW_API int rtw_debug_park_counts(int device, unsigned long long* out
     if (reset) {
         unsigned long long z[3] = {};
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rtw_park_counts), z, sizeof(z)));
+    }
+    return RTW_OK;
+}
+
+// tests: what the first-bounce fills did with their samples (rtw_fill_counts: finished in the fill, bounce records
+// parked, unsolved records parked), summed over the launches since the last reset
+extern "C" RTW_API int rtw_debug_fill_counts(int device, unsigned long long* out3, int reset) {
+    if (!out3) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out3, HIP_SYMBOL(rtw_fill_counts), 3 * sizeof(unsigned long long)));
+    if (reset) {
+        unsigned long long z[3] = {};
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rtw_fill_counts), z, sizeof(z)));
     }
     return RTW_OK;
 }
@@ -4551,6 +4706,21 @@ extern "C" RTW_API int rtw_debug_phase_extra(unsigned long long* out4) {
     return RTW_OK;
 #else
     (void)out4;
+    return rtw::fail(RTW_ERR_UNSUPPORTED, "built without RTW_PHASE_TIMING");
+#endif
+}
+
+// ... and the sums 12..19 (the shade passes split by walk-skipping iterations: RTW_PT_SHADE, RTW_PT_SKIP)
+extern "C" RTW_API int rtw_debug_phase_skip(unsigned long long* out8) {
+#ifdef RTW_PHASE_TIMING
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out8, HIP_SYMBOL(rtw_phase_cycles), 8 * sizeof(unsigned long long),
+                                12 * sizeof(unsigned long long)));
+    unsigned long long z[8] = {};
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rtw_phase_cycles), z, sizeof(z), 12 * sizeof(unsigned long long)));
+    return RTW_OK;
+#else
+    (void)out8;
     return rtw::fail(RTW_ERR_UNSUPPORTED, "built without RTW_PHASE_TIMING");
 #endif
 }
@@ -5002,8 +5172,8 @@ extern "C" RTW_API int rtw_world_kernel_name(rtw_gpu_world* g, char* buf, int ca
     if (g->last_kernel[0] >= 0)  // the product kernel: render_kernel<STATS = false, LDS, LK, TX, GEN, WP>
         std::snprintf(s, sizeof(s), "render_kernel%s<false, %d, %d, %d, %s, %s%s>", g->last_pl ? "_pl" : "", g->last_kernel[0], g->last_kernel[1],
                       g->last_kernel[2], g->last_kernel[4] ? "true" : "false", g->last_kernel[5] ? "true" : "false",
-                      // (the trailing CB of render_kernel_pl's single-sample kernels)
-                      !g->last_pl || g->last_kernel[5] ? "" : g->last_cb ? ", true" : ", false");
+                      // (the trailing CB of render_kernel_pl's single-sample kernels, behind the first bounce's FB)
+                      !g->last_pl || g->last_kernel[5] ? "" : g->last_fb ? ", true, true" : g->last_cb ? ", true" : ", false");
     if ((int)std::strlen(s) >= cap) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "buffer too small");
     std::memcpy(buf, s, std::strlen(s) + 1);
     return RTW_OK;
@@ -5190,7 +5360,7 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
     const int blocks_per_cu = std::max(1, (4 * RTW_MIN_WAVES_PER_SIMD * 64) / RTW_BLOCK);
     size_t cap = std::min({(size_t)RTW_LDS_SCENE_MAX, (size_t)g->lds_max, (size_t)g->lds_cu / blocks_per_cu});
 #ifdef RTW_PHASE_TIMING
-    cap -= (RTW_BLOCK / 64) * (RTW_PT_SUMS + 2) * sizeof(unsigned long long);  // the per-wave phase sums (pt_slot)
+    cap -= (RTW_BLOCK / 64) * (RTW_PT_SUMS + 3) * sizeof(unsigned long long);  // the per-wave phase sums (pt_slot)
 #endif
     const size_t stack_bytes = (size_t)g->depth * RTW_BLOCK * sizeof(int32_t);
     const size_t stack16_bytes = stack_bytes / 2;  // 16-bit entries
@@ -5331,9 +5501,15 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
     const char* cbe = std::getenv("RTW_CAMERA_BATCH");
     const bool cb = pl && !stats && !wp && A.tune == nullptr && A.chunk == 1 && !(cbe && cbe[0] == '0');
     if (cb) kf = fns_cb[tx];
+    // ... and the first bounce in the fill: the solid-texture batch kernel (the TX_ANY one has no registers left
+    // for it); RTW_FIRST_BOUNCE=0: the batch kernel without it
+    const char* fbe = std::getenv("RTW_FIRST_BOUNCE");
+    const bool fb = cb && tx == TX_SOLID && !(fbe && fbe[0] == '0');
+    if (fb) kf = render_kernel_pl<false, 1, LK_SPHERES, TX_SOLID, false, false, true, true>;
     A.park = nullptr;
     if (!stats) {
         g->last_cb = cb ? 1 : 0;
+        g->last_fb = fb ? 1 : 0;
         g->last_pl = pl ? 1 : 0;
         g->last_kernel[0] = mode;
         g->last_kernel[1] = lk;
@@ -5359,7 +5535,7 @@ int launch_render(rtw_gpu_world* g, KArgs& A, int kind, hipStream_t stream, bool
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)per_cu * g->cus));
     if (cb) {  // the park: one record per lane of every resident wave (every launch starts on an empty park)
         const int rc = grow((void**)&g->park, &g->park_bytes,
-                            (size_t)blocks * (RTW_BLOCK / 64) * RTW_PARK_GROUPS * 64 * sizeof(float4));
+                            (size_t)blocks * (RTW_BLOCK / 64) * (fb ? RTW_PARK_GROUPS_FB : RTW_PARK_GROUPS) * 64 * sizeof(float4));
         if (rc != RTW_OK) return rc;
         A.park = g->park;
     }

@@ -210,6 +210,14 @@ class DeviceWorld:
         check(lib().rtw_debug_park_counts(self.device, buf, 1 if reset else 0))
         return tuple(int(v) for v in buf)
 
+    def fill_counts(self, reset: bool = True) -> tuple:
+        """(samples finished in the fill, bounce records parked, unsolved records parked) of the camera batch's
+        first bounce on this world's device, summed over the render launches since the last reset
+        (rtw_debug_fill_counts; tests).  Kernels without the first bounce add nothing."""
+        buf = (C.c_ulonglong * 3)()
+        check(lib().rtw_debug_fill_counts(self.device, buf, 1 if reset else 0))
+        return tuple(int(v) for v in buf)
+
     def last_frame(self) -> dict:
         """The shape of the last frame: render launches, whole-pixel work items (no colour buffer),
         and the dynamic-fetch threshold it ran with (the tuned one once chosen, else the default)."""

@@ -45,11 +45,16 @@ def main():
     fx.restype = C.c_int
     fx.argtypes = [C.POINTER(C.c_ulonglong)]
     ext = (C.c_ulonglong * 4)()
+    fs = lib.rtw_debug_phase_skip
+    fs.restype = C.c_int
+    fs.argtypes = [C.POINTER(C.c_ulonglong)]
+    sk = (C.c_ulonglong * 8)()
+    fs(sk)
     fx(ext)
     fn(buf)
     dw.render_into(p, out.data_ptr(), 0)
     torch.cuda.synchronize()
-    if fx(ext) != 0 or fn(buf) != 0:
+    if fs(sk) != 0 or fx(ext) != 0 or fn(buf) != 0:
         raise SystemExit("library built without RTW_PHASE_TIMING")
     names = {1: "refill", 2: "traversal setup", 3: "traversal", 4: "shading", 5: "sample start",
              6: "samplers", 7: "stores"}
@@ -66,6 +71,19 @@ def main():
           f"setup(camera) {cam / tot:.4f} sample start {buf[5] / tot:.4f} (wave cycles {tot})")
     print(f"refill rounds {rounds} lanes {lanes} mean lanes {mean:.2f} of 64")
     print(f"projection: ({share:.4f}) x (1 - {mean:.2f} / 64) = {share * (1.0 - mean / 64.0):.4f} of the wave cycles",
+          flush=True)
+    # the main loop's shade passes by whether the iteration skipped the walk (camera-only passes): passes, mean
+    # lanes, and the share of the wave cycles that phases 4, 6 and 7 take inside the skipping iterations
+    s_calls, s_lanes, w_calls, w_lanes = sk[0], sk[1], sk[2], sk[3]
+    s_cyc = sk[4] + sk[5] + sk[6]
+    s_mean = s_lanes / s_calls if s_calls else 0.0
+    w_mean = w_lanes / w_calls if w_calls else 0.0
+    s_share = s_cyc / tot
+    print(f"shade passes: walk skipped {s_calls} lanes {s_lanes} mean {s_mean:.2f}; walked {w_calls} lanes {w_lanes} "
+          f"mean {w_mean:.2f}")
+    print(f"cycles in walk-skipping iterations: shading {sk[4]} samplers {sk[5]} stores {sk[6]} "
+          f"share {s_share:.4f} of the wave cycles")
+    print(f"projection: {s_share:.4f} x (1 - {s_mean:.2f} / 64) = {s_share * (1.0 - s_mean / 64.0):.4f} of the wave cycles",
           flush=True)
 
 
