@@ -590,6 +590,80 @@ RTW_API int rtw_aov_resolve(rtw_aov* a, uint32_t channel, float* d_out, void* st
 /* The samples of each pixel that hit something: W*H uint32_t.  Any accumulator, at any point.  Asynchronous. */
 RTW_API int rtw_aov_hits(rtw_aov* a, uint32_t* d_out, void* stream);
 
+/* ---- partitioned AOV accumulators: the AOV pass across GPUs --------------------------------- */
+/* rtw_aov_create_part is rtw_aov_create for one partition of the frame: it reads part_index and
+ * part_count (0 <= part_index < part_count; part_count 0 counts as 1) and takes RTW_LAYOUT_TILES as well as
+ * RTW_LAYOUT_IMAGE (a part has no image of its own either way).  Part (r, N) owns the frame's 8 x 8 tiles
+ * t = r, r + N, ..., the colour accumulators' partition: local tile lt is tile r + lt * N, slots is 64 times its
+ * tile count and the planes are SoA over those slots.  Sample s of pixel p of a part is the whole image's (the
+ * stream is keyed by (seed, pixel, sample); the leaf lists are the frame's, indexed by the frame's tile).  Part
+ * (0, 1) is rtw_aov_create's accumulator exactly: same bits, same launches.  It refuses, naming the field, params
+ * before the world, with nothing allocated: a tile other than 8 x 8 (tile_width / tile_height; 0 counts as 8: a
+ * wave is a tile in this kernel), thread_count > 1 (RTW_ERR_UNSUPPORTED); an unknown layout, a bad part, and what
+ * rtw_aov_create refuses of channels, reserved0 and the size (RTW_ERR_INVALID_ARGUMENT).  part_count may be above
+ * the frame's tile count: such a part holds no tiles, and rtw_aov_add on it launches nothing and still counts
+ * samples, so that the records of a group agree.  rtw_aov_resolve and rtw_aov_hits on an accumulator of
+ * part_count > 1 return RTW_ERR_UNSUPPORTED naming part_count: a part is read through its state or after a merge.
+ * Calls on one AOV accumulator (add, pack, merge, export, import, resolve) stay ordered by the caller: one
+ * stream, or events. */
+RTW_API int rtw_aov_create_part(rtw_gpu_world* gw, const rtw_render_params* params, uint32_t channels, rtw_aov** out);
+
+/* The packed record of an AOV part, in 4-byte words (include/rtw_aov_parts.h has the arithmetic; S0 and T0 are the
+ * slots and tiles of part (0, N), so all N records have one size):
+ *   header   8 words: record version (1), channels, part_index, part_count, samples, slots, tiles, a non-zero magic
+ *            (a colour record holds 0 there: each merge refuses the other's records by name)
+ *   albedo 3 planes, normal 3 planes, depth 1 plane (each if held), hits 1 plane (always): S0 words each
+ * A plane's words past the part's own slots are zero.
+ *
+ * rtw_aov_packed_bytes: the bytes of one such record for params' frame (params' own part is not read), the
+ * channels and part_count parts.  Host only. */
+RTW_API int rtw_aov_packed_bytes(const rtw_render_params* params, uint32_t channels, int32_t part_count, int64_t* bytes);
+/* Copies the accumulator's planes into the device buffer d_packed (4-byte aligned, rtw_aov_packed_bytes for the
+ * accumulator's own part_count): header, planes, zeros in the tails.  Any AOV accumulator, of any part.
+ * Asynchronous on `stream`. */
+RTW_API int rtw_aov_pack(rtw_aov* a, void* d_packed, void* stream);
+/* Replaces all of `whole`'s planes by the merge of part_count records, record r at d_gathered + r * stride_bytes
+ * (stride_bytes a multiple of 4, at least rtw_aov_packed_bytes).  `whole` is of part (0, 1).  First the headers are
+ * read back, after the work already on `stream`, and refused with a message naming the field: stride_bytes; a
+ * record's version, magic, channels (against whole's), part_index (record r holds part r), part_count, slots and
+ * tiles (against the arithmetic); samples, which must be equal in all records.  Nothing is launched or changed on
+ * a refusal.  Then one launch places every plane's tile blocks and whole's samples becomes the records' count:
+ * whole may be resolved or added to as if it had traced the samples itself.  The launch is asynchronous on
+ * `stream`; the call synchronizes it once for the headers.  The records themselves are only read. */
+RTW_API int rtw_aov_merge_parts(rtw_aov* whole, const void* d_gathered, int64_t stride_bytes, int32_t part_count,
+                                void* stream);
+/* The same merge on host arrays, without a GPU: albedo and normal 3 planes of the whole image's slots
+ * (tiles * 64) each, depth and hits one plane; albedo, normal and depth non-null exactly for a channel held.
+ * *samples gets the records' count.  The same refusals; nothing is written on one. */
+RTW_API int rtw_aov_merge_parts_host(const rtw_render_params* params, uint32_t channels, const void* gathered,
+                                     int64_t stride_bytes, int32_t part_count, float* albedo, float* normal, float* depth,
+                                     uint32_t* hits, uint32_t* samples);
+
+/* The state of an AOV accumulator of any part: this header and its planes.  rtw_aov_info stays version 1. */
+typedef struct rtw_aov_state_info { /* all fields fixed-width, no padding; also the checkpoint header */
+    uint32_t version;  /* 1 */
+    uint32_t channels; /* RTW_AOV_* */
+    int32_t width, height;
+    uint32_t samples;
+    int32_t part_index, part_count;
+    uint32_t slots; /* words of one plane: tiles * 64 */
+    uint32_t tiles; /* the part's own tiles */
+    uint32_t reserved; /* 0 */
+    uint64_t seed;
+    uint64_t world_fingerprint;
+} rtw_aov_state_info;
+RTW_API int rtw_aov_get_state_info(rtw_aov* a, rtw_aov_state_info* out); /* host bookkeeping, no sync */
+/* Copies the planes to the host: albedo and normal 3 * slots floats (plane-major, as on the device), depth slots
+ * floats, hits slots counts.  A pointer is non-null exactly for a channel held (hits always).  Padding slots of
+ * edge tiles hold zeros.  Synchronous: it waits for the device, so for every add already issued. */
+RTW_API int rtw_aov_export_state(rtw_aov* a, float* host_albedo, float* host_normal, float* host_depth, uint32_t* host_hits);
+/* Sets the planes and the sample count from an exported state.  Refused with a message naming the field, with
+ * nothing written: any field of `info` that differs from the accumulator's own (samples apart); a hits[slot] above
+ * info->samples; a non-zero word in a padding slot (a slot of an edge tile outside the image) of any plane.
+ * Synchronous. */
+RTW_API int rtw_aov_import_state(rtw_aov* a, const rtw_aov_state_info* info, const float* host_albedo,
+                                 const float* host_normal, const float* host_depth, const uint32_t* host_hits);
+
 /* ---- preview denoiser ---------------------------------------------------------------------- */
 /* A variance-guided a-trous filter for accumulator previews, built on nothing but images:
  * a colour image, the standard error of its channels (rtw_accum_resolve_stderr) and an optional guide of

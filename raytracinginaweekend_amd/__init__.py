@@ -6,7 +6,7 @@ include/rtw.h).  This package is its Python face, mirroring the reference's inte
 Camera.build()..., WorldBuilder / NodeBuilder, demo worlds, rendering.render(...).
 """
 from . import image_io
-from .aov import AovAccumulator, render_aov
+from .aov import AovAccumulator, AovState, render_aov
 from .denoise import Denoiser, denoise_host
 from .progressive import (
     Accumulator,
@@ -45,6 +45,7 @@ __all__ = [
     "AccumState",
     "Accumulator",
     "AovAccumulator",
+    "AovState",
     "AssetSet",
     "BackgroundColor",
     "Camera",

@@ -231,6 +231,23 @@ class AovInfo(C.Structure):  # rtw_aov_info: fixed-width fields, no padding
     ]
 
 
+class AovStateInfo(C.Structure):  # rtw_aov_state_info: fixed-width fields, no padding (also the checkpoint header)
+    _fields_ = [
+        ("version", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("samples", C.c_uint32),
+        ("part_index", C.c_int32),
+        ("part_count", C.c_int32),
+        ("slots", C.c_uint32),
+        ("tiles", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("world_fingerprint", C.c_uint64),
+    ]
+
+
 class DenoiseParams(C.Structure):  # rtw_denoise_params
     _fields_ = [
         ("width", C.c_int32),
@@ -354,6 +371,18 @@ _SIGS = {
     "rtw_aov_get_info": (C.c_int, [_P, C.POINTER(AovInfo)]),
     "rtw_aov_resolve": (C.c_int, [_P, C.c_uint32, _P, _P]),
     "rtw_aov_hits": (C.c_int, [_P, _P, _P]),
+    "rtw_aov_create_part": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.POINTER(_P)]),
+    "rtw_aov_packed_bytes": (C.c_int, [C.POINTER(RenderParams), C.c_uint32, C.c_int32, C.POINTER(C.c_int64)]),
+    "rtw_aov_pack": (C.c_int, [_P, _P, _P]),
+    "rtw_aov_merge_parts": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
+    "rtw_aov_merge_parts_host": (C.c_int, [C.POINTER(RenderParams), C.c_uint32, _P, C.c_int64, C.c_int32,
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rtw_aov_get_state_info": (C.c_int, [_P, C.POINTER(AovStateInfo)]),
+    "rtw_aov_export_state": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_uint32)]),
+    "rtw_aov_import_state": (C.c_int, [_P, C.POINTER(AovStateInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtw_denoiser_run_albedo": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
     "rtw_denoise_host_albedo": (C.c_int, [C.POINTER(DenoiseParams)] + [C.POINTER(C.c_float)] * 6),
     "rtw_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(_P)]),

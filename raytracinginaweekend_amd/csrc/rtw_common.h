@@ -16,7 +16,8 @@ struct rtw_rng {
     rtw_xoro s;
 };
 
-struct rtw_parts_layout;  // include/rtw_parts.h
+struct rtw_parts_layout;      // include/rtw_parts.h
+struct rtw_aov_parts_layout;  // include/rtw_aov_parts.h
 
 namespace rtw {
 
@@ -52,5 +53,12 @@ hipError_t parts_merge_launch(const rtw_parts_layout& L, const void* d_gathered,
                               float* squares, uint32_t* kept, uint32_t* stop, hipStream_t stream);
 // fail() with the message of a refused merge: the field's name and the record (at[0]) and local tile (at[1])
 int parts_refuse(const char* field, const int32_t at[2]);
+// The same for rtw_aov_pack / rtw_aov_merge_parts (include/rtw_aov_parts.h).  planes: the accumulator's albedo,
+// normal and depth planes as held, one after the other, each the accumulator's own slots long; hits: its counts.
+hipError_t aov_parts_pack_launch(const rtw_aov_parts_layout& L, int32_t part_index, uint32_t samples, const float* planes,
+                                 const uint32_t* hits, void* d_packed, hipStream_t stream);
+hipError_t aov_parts_merge_launch(const rtw_aov_parts_layout& L, const void* d_gathered, uint64_t stride_bytes, float* planes,
+                                  uint32_t* hits, hipStream_t stream);
+int aov_parts_refuse(const char* field, int32_t record);
 
 }  // namespace rtw

@@ -38,6 +38,7 @@
 #include "../../include/rtw_adapt.h"
 #include "../../include/rtw_finite.h"
 #include "../../include/rtw_parts.h"
+#include "../../include/rtw_aov_parts.h"
 #include "rtw_common.h"
 
 #ifndef RTW_BLOCK
@@ -3822,6 +3823,9 @@ struct AovArgs {
     const int32_t* pl_count;
     const int32_t* pl_list;
     int32_t pl_cap;
+    // aov_kernel<PL, true> only: the accumulator's part.  Local tile lt = slot >> 6 is tile part_index + lt *
+    // part_count of the frame; the planes stay indexed by the part's own slots, everything else by the frame's tile.
+    int32_t part_index, part_count;
 };
 __device__ __forceinline__ bool aov_slot_pixel(uint32_t slot, int32_t tiles_x, int32_t width, int32_t height, int32_t& px,
                                                int32_t& py) {
@@ -3833,12 +3837,22 @@ __device__ __forceinline__ bool aov_slot_pixel(uint32_t slot, int32_t tiles_x, i
 }
 // PL: the accumulator holds leaf lists (a kernel of its own: the list step's registers cost the walk-only worlds
 // a wave per SIMD, 97 VGPRs against 92)
-template <bool PL>
+// PART: the accumulator is one partition of the frame (rtw_aov_create_part, §5.5i; a kernel of its own for the
+// same reason: the whole-image kernels sit at the last VGPR count of their occupancy and compile as before).  The
+// wave's tile is uniform, so it is read through the first lane and kept in an SGPR.
+template <bool PL, bool PART>
 __global__ __launch_bounds__(RTW_AOV_BLOCK) void aov_kernel(AovArgs A) {
     const DWorld& w = A.w;
     const uint32_t slot = blockIdx.x * RTW_AOV_BLOCK + threadIdx.x;
     int32_t px, py;
-    if (!aov_slot_pixel(slot, A.tiles_x, A.width, A.height, px, py)) return;  // (no barrier below)
+    uint32_t tile = slot >> 6;
+    if (PART) {
+        // a part whose tile count is no multiple of 4 has waves past its slots in the last block; below them
+        // part_index + lt * part_count is a tile of the frame (no overflow: it is below the frame's tile count)
+        if (slot >= A.slots) return;
+        tile = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)((uint32_t)A.part_index + tile * (uint32_t)A.part_count));
+    }
+    if (!aov_slot_pixel(PART ? (tile << 6) | (slot & 63u) : slot, A.tiles_x, A.width, A.height, px, py)) return;  // (no barrier below)
     const uint32_t pix = (uint32_t)(py * A.width + px);
     const float fx = (float)px * A.sx, fy = (float)py * A.sy;
     const ShadeTabs S{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
@@ -3869,9 +3883,9 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void aov_kernel(AovArgs A) {
         // te = succ(t), so the reference DFS reaches the leaf.  An empty list is a miss.  A tie, a failed proof, a
         // ray outside the exact fast division or a tile without a list takes the walk below.
         if (PL) {
-            const int32_t n_list = A.pl_count[slot >> 6];
+            const int32_t n_list = A.pl_count[PART ? tile : slot >> 6];
             if (n_list >= 0 && rp.fast) {
-                const int32_t* __restrict__ L = A.pl_list + (size_t)(slot >> 6) * (uint32_t)A.pl_cap;
+                const int32_t* __restrict__ L = A.pl_list + (size_t)(PART ? tile : slot >> 6) * (uint32_t)A.pl_cap;
                 float ts = F32_INF;  // succ(closest t) once a leaf is found
                 int32_t f = -1;
                 bool tie = false;
@@ -6550,6 +6564,10 @@ struct rtw_aov {
     rtw_aov_info info{};
     int32_t tiles_x = 0;
     uint32_t slots = 0;  // tiles * 64
+    // the part (rtw_aov_create_part; (0, 1): the whole image) and its own tiles t = part_index, part_index +
+    // part_count, ... of the frame's n_tiles
+    int32_t part_index = 0, part_count = 1;
+    uint32_t tiles = 0, n_tiles = 0;
     float* planes = nullptr;  // one allocation: [albedo 3][normal 3][depth 1] planes of `slots` floats, as held
     float* albedo = nullptr;
     float* normal = nullptr;
@@ -6571,6 +6589,9 @@ static void aov_orphan(rtw_aov* a) {
     a->hits = nullptr;
     a->g = nullptr;
 }
+
+static int aov_create_part(rtw_gpu_world* g, const rtw_render_params* p, uint32_t channels, int32_t part_index,
+                           int32_t part_count, rtw_aov** out);
 
 extern "C" RTW_API int rtw_aov_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t channels, rtw_aov** out) {
     if (!p || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
@@ -6594,10 +6615,49 @@ extern "C" RTW_API int rtw_aov_create(rtw_gpu_world* g, const rtw_render_params*
     if (tiles_x * tiles_y * 64 >= (int64_t)0x7FFFFFFF)
         return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.width x height: image too large");
     if (!g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null world");
+    return aov_create_part(g, p, channels, 0, 1, out);
+}
+
+extern "C" RTW_API int rtw_aov_create_part(rtw_gpu_world* g, const rtw_render_params* p, uint32_t channels, rtw_aov** out) {
+    if (!p || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    // (the params first, the world last, as rtw_aov_create)
+    if (p->layout != RTW_LAYOUT_IMAGE && p->layout != RTW_LAYOUT_TILES)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_render_params.layout is unknown");
+    if (p->tile_width != 0 && p->tile_width != 8)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.tile_width: an AOV part takes 8 x 8 tiles (a wave is a tile)");
+    if (p->tile_height != 0 && p->tile_height != 8)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.tile_height: an AOV part takes 8 x 8 tiles (a wave is a tile)");
+    if (p->thread_count > 1)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.thread_count: AOV accumulators take 0 or 1 (no sample planes)");
+    const int32_t part_count = p->part_count > 0 ? p->part_count : 1;
+    if (p->part_count < 0 || p->part_index < 0 || p->part_index >= part_count)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_render_params.part_index must be within 0 .. part_count - 1");
+    if (channels == 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channels is 0: name at least one RTW_AOV_* channel");
+    if (channels & ~(RTW_AOV_ALBEDO | RTW_AOV_NORMAL | RTW_AOV_DEPTH))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channels holds an unknown bit");
+    if (p->reserved0 != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_render_params.reserved0 must be 0");
+    if (p->width < 2 || p->height < 2)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_render_params.width and height must be >= 2");
+    if ((((int64_t)p->width + 7) / 8) * (((int64_t)p->height + 7) / 8) * 64 >= (int64_t)0x7FFFFFFF)
+        return rtw::fail(RTW_ERR_UNSUPPORTED, "rtw_render_params.width x height: image too large");
+    if (!g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null world");
+    return aov_create_part(g, p, channels, p->part_index, part_count, out);
+}
+
+// the accumulator of part (part_index, part_count) of p's frame; the callers have checked everything
+static int aov_create_part(rtw_gpu_world* g, const rtw_render_params* p, uint32_t channels, int32_t part_index,
+                           int32_t part_count, rtw_aov** out) {
+    const int64_t tiles_x = ((int64_t)p->width + 7) / 8, tiles_y = ((int64_t)p->height + 7) / 8;
+    const int64_t n_tiles = tiles_x * tiles_y;
     auto* a = new rtw_aov;
     a->g = g;
     a->tiles_x = (int32_t)tiles_x;
-    a->slots = (uint32_t)(tiles_x * tiles_y * 64);
+    a->part_index = part_index;
+    a->part_count = part_count;
+    a->n_tiles = (uint32_t)n_tiles;
+    a->tiles = n_tiles > part_index ? (uint32_t)((n_tiles - part_index + part_count - 1) / part_count) : 0u;
+    a->slots = a->tiles * 64u;
     rtw_aov_info& I = a->info;
     I.version = 1;
     I.channels = channels;
@@ -6611,8 +6671,10 @@ extern "C" RTW_API int rtw_aov_create(rtw_gpu_world* g, const rtw_render_params*
     const size_t n_planes = ((channels & RTW_AOV_ALBEDO) ? 3 : 0) + ((channels & RTW_AOV_NORMAL) ? 3 : 0) +
                             ((channels & RTW_AOV_DEPTH) ? 1 : 0);
     const size_t plane_bytes = (size_t)a->slots * sizeof(float);
-    hipError_t e = hipMalloc(&a->planes, n_planes * plane_bytes);
-    if (e == hipSuccess) e = hipMalloc(&a->hits, plane_bytes);
+    // (a part without tiles, part_count above the frame's tile count, holds nothing: no plane, no list, no launch)
+    const bool holds = a->slots > 0;
+    hipError_t e = holds ? hipMalloc(&a->planes, n_planes * plane_bytes) : hipSuccess;
+    if (e == hipSuccess && holds) e = hipMalloc(&a->hits, plane_bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         aov_orphan(a);
@@ -6624,13 +6686,14 @@ extern "C" RTW_API int rtw_aov_create(rtw_gpu_world* g, const rtw_render_params*
     if (channels & RTW_AOV_NORMAL) a->normal = next, next += 3 * (size_t)a->slots;
     if (channels & RTW_AOV_DEPTH) a->depth = next;
     // (synchronous: the zeros are there before any stream's first add)
-    e = hipMemset(a->planes, 0, n_planes * plane_bytes);
-    if (e == hipSuccess) e = hipMemset(a->hits, 0, plane_bytes);
+    if (holds) e = hipMemset(a->planes, 0, n_planes * plane_bytes);
+    if (e == hipSuccess && holds) e = hipMemset(a->hits, 0, plane_bytes);
     // The camera rays' leaf lists, where the megakernel would use them (ensure_primary_lists): a world of plain
     // cullable spheres whose SAH tables hold the leaves' proof boxes, rays that admit the exact fast division.
     // RTW_PRIMARY_LISTS=0 switches them off here too, RTW_PRIMARY_LIST_CAP sets the longest list.
     const char* pl_env = std::getenv("RTW_PRIMARY_LISTS");
-    if (e == hipSuccess && g->pl_scope && g->mk_world && g->sah_nodes > 0 && g->leaf_count >= 1 &&
+    // (a part keeps the lists of the whole frame, indexed by the frame's tile, as the megakernel does)
+    if (e == hipSuccess && holds && g->pl_scope && g->mk_world && g->sah_nodes > 0 && g->leaf_count >= 1 &&
         (pl_env ? pl_env[0] == '1' : RTW_PL_DEFAULT != 0)) {
         const int32_t cap = (int32_t)std::min<size_t>((size_t)g->leaf_count, env_size("RTW_PRIMARY_LIST_CAP", RTW_BEAM_CAP_DEFAULT));
         const size_t n = (size_t)(tiles_x * tiles_y);
@@ -6712,17 +6775,30 @@ extern "C" RTW_API int rtw_aov_add(rtw_aov* a, uint32_t n, void* stream) {
     A.pl_count = a->pl_buf;
     A.pl_list = a->pl_buf ? a->pl_buf + (size_t)a->pl_tiles : nullptr;
     A.pl_cap = a->pl_cap;
+    A.part_index = a->part_index;
+    A.part_count = a->part_count;
     // the stack: one int32_t per level of the reference tree and lane (g->depth >= that tree's depth, <= RTW_STACK)
     const size_t lds = (size_t)std::max(1, g->depth) * RTW_AOV_BLOCK * sizeof(int32_t);
-    const dim3 grid((a->slots + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK);
-    if (A.pl_count) hipLaunchKernelGGL(aov_kernel<true>, grid, dim3(RTW_AOV_BLOCK), lds, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(aov_kernel<false>, grid, dim3(RTW_AOV_BLOCK), lds, (hipStream_t)stream, A);
+    const dim3 grid((a->slots + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK), block(RTW_AOV_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    if (a->slots == 0) {  // a part without tiles: nothing to trace, and the count goes on as the group's does
+    } else if (a->part_count == 1) {  // the whole image: the kernels as they were
+        if (A.pl_count) hipLaunchKernelGGL((aov_kernel<true, false>), grid, block, lds, s, A);
+        else hipLaunchKernelGGL((aov_kernel<false, false>), grid, block, lds, s, A);
+    } else {
+        if (A.pl_count) hipLaunchKernelGGL((aov_kernel<true, true>), grid, block, lds, s, A);
+        else hipLaunchKernelGGL((aov_kernel<false, true>), grid, block, lds, s, A);
+    }
     HIP_TRY(hipGetLastError());
     a->info.samples += n;
     return RTW_OK;
 }
 
 namespace {
+int aov_refuse_part() {
+    return rtw::fail(RTW_ERR_UNSUPPORTED, "part_count: the AOV accumulator holds one partition of the image; read it through "
+                                          "its state (rtw_aov_export_state) or after rtw_aov_merge_parts");
+}
 int aov_resolve(rtw_aov* a, int what, const float* planes, void* d_out, hipStream_t stream) {
     HIP_TRY(hipSetDevice(a->g->device));
     const uint32_t pixels = (uint32_t)a->info.width * (uint32_t)a->info.height;
@@ -6739,6 +6815,7 @@ extern "C" RTW_API int rtw_aov_resolve(rtw_aov* a, uint32_t channel, float* d_ou
     if (channel != RTW_AOV_ALBEDO && channel != RTW_AOV_NORMAL && channel != RTW_AOV_DEPTH)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channel is not one of RTW_AOV_ALBEDO, RTW_AOV_NORMAL, RTW_AOV_DEPTH");
     if (!(a->info.channels & channel)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "channel: the AOV accumulator does not hold it");
+    if (a->part_count > 1) return aov_refuse_part();
     if (a->info.samples < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "resolve needs samples >= 1");
     const float* planes = channel == RTW_AOV_ALBEDO ? a->albedo : channel == RTW_AOV_NORMAL ? a->normal : a->depth;
     return aov_resolve(a, channel == RTW_AOV_DEPTH ? 1 : 0, planes, d_out, (hipStream_t)stream);
@@ -6747,7 +6824,176 @@ extern "C" RTW_API int rtw_aov_resolve(rtw_aov* a, uint32_t channel, float* d_ou
 extern "C" RTW_API int rtw_aov_hits(rtw_aov* a, uint32_t* d_out, void* stream) {
     if (!a || !d_out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    if (a->part_count > 1) return aov_refuse_part();
     return aov_resolve(a, 2, nullptr, d_out, (hipStream_t)stream);
+}
+
+// ---- AOV partition records and state (rtw.h; include/rtw_aov_parts.h).  The kernels are rtw_parts.hip's. ----
+namespace {
+// the layout of the records of a's group, checked against a's own geometry
+int aov_layout(const rtw_aov* a, int32_t part_count, rtw_aov_parts_layout* L) {
+    rtw_render_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = a->info.width;
+    p.height = a->info.height;
+    if (rtw_aov_parts_layout_of(&p, a->info.channels, part_count, L) != 0) return rtw::aov_parts_refuse("params", 0);
+    if ((uint32_t)L->n_tiles != a->n_tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad AOV accumulator geometry");
+    return RTW_OK;
+}
+
+void aov_state_info(const rtw_aov* a, rtw_aov_state_info* I) {
+    std::memset(I, 0, sizeof(*I));
+    I->version = 1;
+    I->channels = a->info.channels;
+    I->width = a->info.width;
+    I->height = a->info.height;
+    I->samples = a->info.samples;
+    I->part_index = a->part_index;
+    I->part_count = a->part_count;
+    I->slots = a->slots;
+    I->tiles = a->tiles;
+    I->seed = a->info.seed;
+    I->world_fingerprint = a->info.world_fingerprint;
+}
+
+// a pointer is non-null exactly for a channel held
+int aov_state_pointers(const rtw_aov* a, const void* albedo, const void* normal, const void* depth) {
+    const struct {
+        uint32_t bit;
+        const void* p;
+        const char* name;
+    } want[3] = {{RTW_AOV_ALBEDO, albedo, "albedo"}, {RTW_AOV_NORMAL, normal, "normal"}, {RTW_AOV_DEPTH, depth, "depth"}};
+    for (const auto& w : want) {
+        const bool has = (a->info.channels & w.bit) != 0;
+        if (has && !w.p) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("null ") + w.name + " (the AOV accumulator holds the channel)");
+        if (!has && w.p) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(w.name) + " given, but the AOV accumulator does not hold the channel");
+    }
+    return RTW_OK;
+}
+}  // namespace
+
+extern "C" RTW_API int rtw_aov_pack(rtw_aov* a, void* d_packed, void* stream) {
+    if (!a || !d_packed) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    if (((uintptr_t)d_packed & 3u) != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "d_packed must be 4-byte aligned");
+    rtw_aov_parts_layout L;
+    const int rc = aov_layout(a, a->part_count, &L);
+    if (rc != RTW_OK) return rc;
+    if ((uint32_t)rtw_aov_parts_tiles(&L, a->part_index) != a->tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad AOV accumulator geometry");
+    HIP_TRY(hipSetDevice(a->g->device));
+    HIP_TRY(rtw::aov_parts_pack_launch(L, a->part_index, a->info.samples, a->planes, a->hits, d_packed, (hipStream_t)stream));
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_aov_merge_parts(rtw_aov* whole, const void* d_gathered, int64_t stride_bytes, int32_t part_count,
+                                           void* stream_) {
+    rtw_aov* a = whole;
+    if (!a || !d_gathered) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    if (a->part_index != 0 || a->part_count != 1)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "a merge fills the whole image's AOV accumulator: part_index / part_count is not 0 / 1");
+    hipStream_t stream = (hipStream_t)stream_;
+    rtw_aov_parts_layout L;
+    const int rc = aov_layout(a, part_count, &L);
+    if (rc != RTW_OK) return rc;
+    if (stride_bytes < (int64_t)(L.words * 4) || stride_bytes % 4 != 0 || ((uintptr_t)d_gathered & 3u) != 0)
+        return rtw::aov_parts_refuse("stride_bytes", 0);
+    // The headers come back first, after the work already on `stream` (the packs, or the collective that filled
+    // the buffer): everything is refused before anything is launched.
+    HIP_TRY(hipSetDevice(a->g->device));
+    std::vector<uint32_t> host((size_t)part_count * RTW_PARTS_HEADER_WORDS);
+    for (int32_t r = 0; r < part_count; ++r)
+        HIP_TRY(hipMemcpyAsync(host.data() + (size_t)r * RTW_PARTS_HEADER_WORDS, (const char*)d_gathered + (size_t)r * (size_t)stride_bytes,
+                               RTW_PARTS_HEADER_WORDS * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    uint32_t samples = 0;
+    const char* field = nullptr;
+    int32_t at = 0;
+    if (rtw_aov_parts_check(&L, host.data(), RTW_PARTS_HEADER_WORDS, &samples, &field, &at) != 0) return rtw::aov_parts_refuse(field, at);
+    HIP_TRY(rtw::aov_parts_merge_launch(L, d_gathered, (uint64_t)stride_bytes, a->planes, a->hits, stream));
+    a->info.samples = samples;
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_aov_get_state_info(rtw_aov* a, rtw_aov_state_info* out) {
+    if (!a || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    aov_state_info(a, out);
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_aov_export_state(rtw_aov* a, float* host_albedo, float* host_normal, float* host_depth,
+                                            uint32_t* host_hits) {
+    if (!a || !host_hits) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    const int rc = aov_state_pointers(a, host_albedo, host_normal, host_depth);
+    if (rc != RTW_OK) return rc;
+    HIP_TRY(hipSetDevice(a->g->device));
+    HIP_TRY(hipDeviceSynchronize());  // (the adds may be on any stream)
+    const size_t plane = (size_t)a->slots * sizeof(float);
+    if (plane == 0) return RTW_OK;
+    if (host_albedo) HIP_TRY(hipMemcpy(host_albedo, a->albedo, 3 * plane, hipMemcpyDeviceToHost));
+    if (host_normal) HIP_TRY(hipMemcpy(host_normal, a->normal, 3 * plane, hipMemcpyDeviceToHost));
+    if (host_depth) HIP_TRY(hipMemcpy(host_depth, a->depth, plane, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_hits, a->hits, plane, hipMemcpyDeviceToHost));
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_aov_import_state(rtw_aov* a, const rtw_aov_state_info* info, const float* host_albedo,
+                                            const float* host_normal, const float* host_depth, const uint32_t* host_hits) {
+    if (!a || !info || !host_hits) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
+    const int rc = aov_state_pointers(a, host_albedo, host_normal, host_depth);
+    if (rc != RTW_OK) return rc;
+    rtw_aov_state_info M;
+    aov_state_info(a, &M);
+    auto differs = [](const char* field) {
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("AOV state does not match the accumulator: ") + field + " differs");
+    };
+    if (info->version != M.version) return differs("version");
+    if (info->channels != M.channels) return differs("channels");
+    if (info->width != M.width) return differs("width");
+    if (info->height != M.height) return differs("height");
+    if (info->part_index != M.part_index) return differs("part_index");
+    if (info->part_count != M.part_count) return differs("part_count");
+    if (info->slots != M.slots) return differs("slots");
+    if (info->tiles != M.tiles) return differs("tiles");
+    if (info->reserved != M.reserved) return differs("reserved");
+    if (info->seed != M.seed) return differs("seed");
+    if (info->world_fingerprint != M.world_fingerprint) return differs("world_fingerprint");
+    // hits at most the sample count; zero in every plane where no pixel is
+    const struct {
+        const uint32_t* p;
+        int planes;
+        const char* name;
+    } held[4] = {{(const uint32_t*)host_albedo, 3, "albedo"}, {(const uint32_t*)host_normal, 3, "normal"},
+                 {(const uint32_t*)host_depth, 1, "depth"}, {host_hits, 1, "hits"}};
+    for (uint32_t slot = 0; slot < a->slots; ++slot) {
+        const uint32_t tile = (uint32_t)a->part_index + (slot >> 6) * (uint32_t)a->part_count;
+        const int32_t px = (int32_t)(tile % (uint32_t)a->tiles_x) * 8 + (int32_t)(slot & 7u);
+        const int32_t py = (int32_t)(tile / (uint32_t)a->tiles_x) * 8 + (int32_t)((slot >> 3) & 7u);
+        if (px < M.width && py < M.height) {
+            if (host_hits[slot] > info->samples)
+                return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "hits[" + std::to_string(slot) + "] = " + std::to_string(host_hits[slot]) +
+                                                               " is above the state's samples (" + std::to_string(info->samples) + ")");
+            continue;
+        }
+        for (const auto& h : held)
+            for (int k = 0; h.p && k < h.planes; ++k)
+                if (h.p[(size_t)k * a->slots + slot] != 0u)
+                    return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(h.name) + "[" + std::to_string((size_t)k * a->slots + slot) +
+                                                                   "]: a padding slot holds 0");
+    }
+    HIP_TRY(hipSetDevice(a->g->device));
+    HIP_TRY(hipDeviceSynchronize());  // (a running add of this accumulator, on any stream)
+    const size_t plane = (size_t)a->slots * sizeof(float);
+    if (plane > 0) {
+        if (host_albedo) HIP_TRY(hipMemcpy(a->albedo, host_albedo, 3 * plane, hipMemcpyHostToDevice));
+        if (host_normal) HIP_TRY(hipMemcpy(a->normal, host_normal, 3 * plane, hipMemcpyHostToDevice));
+        if (host_depth) HIP_TRY(hipMemcpy(a->depth, host_depth, plane, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(a->hits, host_hits, plane, hipMemcpyHostToDevice));
+    }
+    a->info.samples = info->samples;
+    return RTW_OK;
 }
 
 namespace {

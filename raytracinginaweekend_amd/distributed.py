@@ -16,6 +16,9 @@ in one process; here the ranks own disjoint pixels, so the merge is a placement)
 DistributedAccumulator is the same idea for progressive accumulators (progressive.py): every rank adds to its own
 partition's accumulator, and one gather of packed state records plus one merge launch (include/rtw_parts.h) gives
 rank 0 the whole image's accumulator, with its noise estimate, stop map, kept counts, denoiser and checkpoint.
+
+DistributedAovAccumulator does the same for the first-hit AOV pass (aov.py, include/rtw_aov_parts.h): the denoiser's
+guide and albedo images are traced an N-th per rank and merged on rank 0, beside the colour accumulator's state.
 """
 from __future__ import annotations
 
@@ -259,6 +262,82 @@ class DistributedAccumulator:
             return self.whole
         self.local.pack_into(self.record, self._stream())
         if self._device_collectives():
+            gather_records(self.record, self.gathered, self.rank, self.world_size)
+        else:  # stage through the host on both sides
+            host = self.record.cpu()
+            staged = self.torch.zeros(self.gathered.numel(), dtype=self.torch.int32) if self.rank == 0 else None
+            gather_records(host, staged, self.rank, self.world_size)
+            if self.rank == 0:
+                self.gathered.copy_(staged)
+        if self.rank != 0:
+            return None
+        self.whole.merge_parts(self.gathered, self.stride_bytes, self.world_size, self._stream())
+        return self.whole
+
+
+class DistributedAovAccumulator:
+    """The first-hit AOV accumulator of one frame across the ranks of a process group (one process per GPU): the
+    guide and albedo images of `DistributedAccumulator`'s denoised preview, traced an N-th per rank.
+
+    Rank r owns an `AovAccumulator` of part (r, world_size) (`local`); rank 0 also owns `whole`, a plain
+    `AovAccumulator` on the same `DeviceWorld`.  `add` is local and asynchronous; `sync` packs every rank's planes,
+    gathers the records onto rank 0 with one collective and merges them into `whole`, which then is, bit for bit,
+    the accumulator one GPU would hold after the same adds: resolve it, or hand it to `Accumulator.denoised`.
+    With the nccl backend the device tensors are gathered; with any other (gloo) the record is staged through a
+    host tensor on both sides, which also lets several ranks share one GPU.  world_size 1 is a pass-through
+    without a collective: `local` is `whole`.  Pass the `DeviceWorld` of the colour accumulator to share its
+    resident world.
+
+    `sync` may be called any number of times; adds after it continue the partitions (not `whole`)."""
+
+    def __init__(self, world: World | DeviceWorld, size: Size2i, rank: int = 0, world_size: int = 1, device: int = 0, *,
+                 seed: int = DEFAULT_SEED, channels=("albedo", "normal", "depth")):
+        import torch
+
+        from .aov import AovAccumulator
+
+        if not 0 <= rank < world_size:
+            raise ValueError("rank must be within 0 .. world_size - 1")
+        self.torch = torch
+        self.rank, self.world_size = rank, world_size
+        self.dev = torch.device("cuda", device)
+        self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
+        kw = dict(seed=seed, device=device, channels=channels)
+        self.whole = AovAccumulator(self.dworld, size, **kw) if rank == 0 else None
+        if world_size == 1:
+            self.local = self.whole
+        else:
+            self.local = AovAccumulator(self.dworld, size, part=(rank, world_size), **kw)
+            # (a stride of whole 16 bytes: every record of the gathered buffer takes the merge's 16-byte path)
+            self.stride_bytes = -(-self.local.packed_bytes() // 16) * 16
+            self.record = torch.zeros(self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
+            self.gathered = (torch.zeros(world_size * self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
+                             if rank == 0 else None)
+        self.samples = 0
+
+    def release(self) -> None:
+        for a in {id(a): a for a in (self.local, self.whole) if a is not None}.values():
+            a.release()
+        self.local = self.whole = None
+
+    def _stream(self) -> int:
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def add(self, n: int) -> None:
+        """The next `n` camera samples of this rank's pixels (asynchronous)."""
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        self.local.add(n, self._stream())
+        self.samples += n
+
+    def sync(self):
+        """Pack, one gather onto rank 0, merge: returns `whole` on rank 0 and None elsewhere.  Every rank calls it."""
+        import torch.distributed as dist
+
+        if self.world_size == 1:
+            return self.whole
+        self.local.pack_into(self.record, self._stream())
+        if dist.get_backend() == "nccl":
             gather_records(self.record, self.gathered, self.rank, self.world_size)
         else:  # stage through the host on both sides
             host = self.record.cpu()
