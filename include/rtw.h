@@ -202,6 +202,42 @@ typedef struct rtw_world {
     const rtw_perlin* perlins;
 } rtw_world;
 
+/* The deepest BVH the device walks: nodes on the longest root-to-leaf path (its per-lane stack). */
+#define RTW_MAX_BVH_DEPTH 32
+/* The longest texture chain the device follows: checkers in a row plus the texture that ends them. */
+#define RTW_MAX_TEXTURE_CHAIN 64
+
+/* The validator every upload runs first (host only: it needs no device and touches none).  It reads
+ * `world` and nothing else, follows no index before it has checked it, and answers
+ *   RTW_OK                    *depth (when not NULL) = nodes on the longest root-to-leaf path, 0 for a
+ *                             one-leaf world; every read the device and the oracle make of the tables
+ *                             is then in bounds;
+ *   RTW_ERR_INVALID_ARGUMENT  the world is not one the reference can express (list below);
+ *   RTW_ERR_UNSUPPORTED       a well-formed tree deeper than RTW_MAX_BVH_DEPTH.
+ * On an error rtw_last_error() reads "invalid world: <table>[<index>].<field> <what>" (no index for the
+ * world's own fields: "invalid world: root ...", "invalid world: light.plane ...") and *depth is left alone.
+ * A world is accepted when
+ *   - every count is >= 0, leaf_count >= 1, and every table with a count > 0 has its pointer;
+ *   - root is a node index < node_count, or ~leaf of a leaf < leaf_count;
+ *   - the nodes reachable from root form a binary tree: axis 0..2, children in range, every node and every
+ *     leaf referenced exactly once (the reference's builder makes no other tree: none shared, none left
+ *     out, no cycle), so node_count == leaf_count - 1;
+ *   - leaves: geom_kind 0..3, geom_index inside that kind's table, material < material_count, no flag
+ *     above RTW_LEAF_ANIMATION;
+ *   - materials: kind 0..4 and, except for a dielectric (whose texture is ignored, -1 by convention),
+ *     texture < texture_count;
+ *   - textures: kind 0..3; a checker's even and odd, an image texture's image and a marble's perlin inside
+ *     their tables (the fields a kind does not use are ignored); checkers form no cycle and no chain of
+ *     more than RTW_MAX_TEXTURE_CHAIN textures, the one that ends it included;
+ *   - perlins: bits 1..8 and perm_x / perm_y / perm_z [0 .. 2^bits) all < 2^bits (the rest is never read);
+ *   - images: width, height >= 1 and rgb not NULL;
+ *   - rects[].plane, and light.plane when has_light (0 or 1), are RTW_PLANE_*; a light's r0 and r1 are
+ *     increasing ranges within +-2^30 (the reference samples them with gen_range, which panics otherwise);
+ *   - camera.time0 <= camera.time1, both finite and their difference too (gen_range again, unless equal);
+ *   - node bounds, sphere centres and radii, rect distances, leaf offsets, leaf velocity x the largest
+ *     ray time, and the camera position are no NaN and at most 2^30 in magnitude. */
+RTW_API int rtw_world_check(const rtw_world* world, int32_t* depth);
+
 /* ---- render parameters ------------------------------------------------------------------- */
 typedef struct rtw_render_params {
     int32_t width, height;      /* image_size: Size2i (width, height >= 2) */

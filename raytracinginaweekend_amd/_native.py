@@ -332,6 +332,7 @@ _SIGS = {
     "rtw_multi_release": (C.c_int, [_P]),
     "rtw_multi_peer_copies": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "rtw_world_fingerprint": (C.c_int, [C.POINTER(World), C.POINTER(C.c_uint64)]),
+    "rtw_world_check": (C.c_int, [C.POINTER(World), C.POINTER(C.c_int32)]),
     "rtw_accum_create": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.POINTER(_P)]),
     "rtw_accum_release": (C.c_int, [_P]),
     "rtw_accum_add": (C.c_int, [_P, C.c_uint32, _P]),

@@ -4196,84 +4196,9 @@ bool material_reads_uv(const rtw_world* w, int m) {
     return false;
 }
 
-int check_world(const rtw_world* w, int* depth_out) {
-    if (!w) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null world");
-    if (w->leaf_count < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "world has no leaves");
-    auto bad = [&](const char* m) { return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("invalid world: ") + m); };
-    if (w->root >= 0 ? w->root >= w->node_count : (-1 - w->root) >= w->leaf_count) return bad("root out of range");
-    for (int i = 0; i < w->leaf_count; ++i) {
-        const rtw_leaf& L = w->leaves[i];
-        const int counts[4] = {w->sphere_count, w->rect_count, w->box_count, w->triangle_count};
-        if (L.geom_kind < 0 || L.geom_kind > 3) return bad("leaf geometry kind");
-        if (L.geom_index < 0 || L.geom_index >= counts[L.geom_kind]) return bad("leaf geometry index");
-        if (L.material < 0 || L.material >= w->material_count) return bad("leaf material index");
-    }
-    for (int i = 0; i < w->material_count; ++i) {
-        const rtw_material& m = w->materials[i];
-        if (m.kind < 0 || m.kind > 4) return bad("material kind");
-        if (m.kind != RTW_MAT_DIELECTRIC && (m.texture < 0 || m.texture >= w->texture_count)) return bad("material texture");
-    }
-    for (int i = 0; i < w->texture_count; ++i) {
-        const rtw_texture& t = w->textures[i];
-        if (t.kind == RTW_TEX_CHECKER && (t.even < 0 || t.even >= w->texture_count || t.odd < 0 || t.odd >= w->texture_count))
-            return bad("checker texture ids");
-        if (t.kind == RTW_TEX_IMAGE && (t.image < 0 || t.image >= w->image_count)) return bad("image id");
-        if (t.kind == RTW_TEX_MARBLE && (t.perlin < 0 || t.perlin >= w->perlin_count)) return bad("perlin id");
-    }
-    for (int i = 0; i < w->perlin_count; ++i)
-        if (w->perlins[i].bits < 1 || w->perlins[i].bits > 8) return bad("perlin bits");
-    for (int i = 0; i < w->image_count; ++i)
-        if (w->images[i].width < 1 || w->images[i].height < 1 || !w->images[i].rgb) return bad("image");
-    // coordinate bound behind the exact fast division of the slab test (|a| <= 2^40 there):
-    // every coordinate the device sees stays below 2^30 in magnitude
-    const float LIM = 1073741824.0f;
-    auto big = [&](const float* v, int n) {
-        for (int k = 0; k < n; ++k)
-            if (!(v[k] >= -LIM && v[k] <= LIM)) return true;
-        return false;
-    };
-    for (int i = 0; i < w->node_count; ++i)
-        if (big(w->nodes[i].min, 3) || big(w->nodes[i].max, 3)) return bad("node bounds beyond 2^30");
-    for (int i = 0; i < w->sphere_count; ++i)
-        if (big(w->spheres[i].center, 4)) return bad("sphere beyond 2^30");
-    for (int i = 0; i < w->rect_count; ++i)
-        if (big(&w->rects[i].dist, 1)) return bad("rect beyond 2^30");
-    // an Animation offset is velocity x ray time, the rolling shutter's pace included (rtw_ray_time_range)
-    float rt0 = 0.0f, rt1 = 0.0f;
-    const float tmax = rtw_ray_time_range(&w->camera, &rt0, &rt1) ? std::max(std::fabs(rt0), std::fabs(rt1))
-                                                                   : std::numeric_limits<float>::infinity();
-    for (int i = 0; i < w->leaf_count; ++i) {
-        const rtw_leaf& L = w->leaves[i];
-        float vt[3];
-        for (int k = 0; k < 3; ++k)
-            vt[k] = (L.flags & RTW_LEAF_ANIMATION) && L.velocity[k] != 0.0f ? L.velocity[k] * tmax : 0.0f;
-        if (big(L.offset, 3) || big(vt, 3)) return bad("leaf transform beyond 2^30");
-    }
-    if (big(w->camera.position, 3)) return bad("camera beyond 2^30");
-    // node references + depth (the per-lane stack holds one entry per level)
-    std::vector<std::pair<int32_t, int>> todo;
-    int maxd = 0;
-    std::vector<uint8_t> seen((size_t)std::max(1, w->node_count), 0);
-    if (w->root >= 0) todo.emplace_back(w->root, 0);
-    while (!todo.empty()) {
-        auto [n, d] = todo.back();
-        todo.pop_back();
-        if (n < 0) {
-            if (-1 - n >= w->leaf_count) return bad("leaf reference");
-            continue;
-        }
-        if (n >= w->node_count || seen[(size_t)n]) return bad("node reference");
-        seen[(size_t)n] = 1;
-        const rtw_bvh_node& nd = w->nodes[n];
-        if (nd.axis < 0 || nd.axis > 2) return bad("node axis");
-        maxd = std::max(maxd, d + 1);
-        todo.emplace_back(nd.left, d + 1);
-        todo.emplace_back(nd.right, d + 1);
-    }
-    if (maxd > RTW_STACK) return rtw::fail(RTW_ERR_UNSUPPORTED, "BVH deeper than the device stack");
-    *depth_out = maxd;
-    return RTW_OK;
-}
+// The validator is host code of its own (rtw_check.cpp, rtw_world_check): every caller below goes through it.
+static_assert(RTW_STACK == RTW_MAX_BVH_DEPTH, "rtw.h promises the depth the per-lane stack holds");
+int check_world(const rtw_world* w, int* depth_out) { return rtw_world_check(w, depth_out); }
 
 // The SAH path's tables (§5.5), or empty when the world does not qualify: no volume leaves (their
 // RNG draws depend on the visit order), every leaf cullable with its true world box (rtw_cull_leaf,
@@ -4987,7 +4912,10 @@ extern "C" RTW_API int rtw_world_upload(const rtw_world* w, int device, rtw_gpu_
         g->depth = std::max(g->depth, sah.depth);
     }
     g->tri_count = w->triangle_count;
-    g->tri_prefix = tri_prefix_of(w);
+    // (a one-leaf world has no node records for the prefix's made-up leaf records to stand in: launch_render
+    // needs tri_prefix <= 2 * nodes, which every world of two or more leaves meets with its L - 1 nodes -- a
+    // one-triangle world keeps its leaf record, where launch_render used to answer RTW_ERR_UNSUPPORTED)
+    g->tri_prefix = std::min(tri_prefix_of(w), 2 * w->node_count);
     if (g->tri_prefix > 0) {
         g->tri_prefix_mat = li[0].z;
         g->tri_prefix_w = li[0].w;

@@ -138,6 +138,14 @@ class BackgroundColor:
         return b
 
 
+def check_world(raw: N.World) -> int:
+    """rtw_world_check on any rtw_world (host only, no device): the depth of its BVH (0: one leaf), or
+    RtwError whose message names the table, the index and the field (the contract is include/rtw.h's)."""
+    depth = C.c_int32(-1)
+    check(lib().rtw_world_check(C.byref(raw), C.byref(depth)))
+    return depth.value
+
+
 # ------------------------------------------------------------------------------------------------
 # The finished world (rendering.rs:12-17), owned by the C++ side
 # ------------------------------------------------------------------------------------------------
@@ -163,6 +171,10 @@ class World:
 
     def ptr(self):
         return C.byref(self.raw)
+
+    def check(self) -> int:
+        """rtw_world_check: the BVH depth, or RtwError with the table and field the validator refused."""
+        return check_world(self.raw)
 
     # convenience views (copies) for tests
     def nodes(self) -> np.ndarray:
