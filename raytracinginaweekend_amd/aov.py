@@ -24,14 +24,15 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
+from . import _parts
 from ._native import check, lib
 from .rendering import DEFAULT_SEED, DeviceWorld, Size2i, render_params
 from .world import World
 
 _CHANNELS = {"albedo": N.AOV_ALBEDO, "normal": N.AOV_NORMAL, "depth": N.AOV_DEPTH}
 
-RECORD_VERSION = 1  # RTW_AOV_PARTS_VERSION
-RECORD_HEADER_WORDS = 8
+RECORD_VERSION = _parts.VERSION  # RTW_PARTS_VERSION
+RECORD_HEADER_WORDS = _parts.HEADER_WORDS
 RECORD_MAGIC = 0x564F4152  # RTW_AOV_PARTS_MAGIC
 PER_TILE = 64  # a wave is an 8 x 8 tile
 
@@ -46,24 +47,10 @@ def frame_tiles(width: int, height: int) -> int:
 def record_layout(width: int, height: int, channels: int, part_count: int) -> dict:
     """The packed record of include/rtw_aov_parts.h in numpy's terms: n_tiles, tiles0, slots0, the word offsets
     albedo / normal / depth (None: the channel is not held) / hits, planes and words."""
-    n_tiles = frame_tiles(width, height)
-    tiles0 = -(-n_tiles // part_count)
-    slots0 = tiles0 * PER_TILE
-    at = RECORD_HEADER_WORDS
-    lay = {"n_tiles": n_tiles, "tiles0": tiles0, "slots0": slots0, "planes": 0}
-    for name, count in _PLANES:
-        held = name == "hits" or bool(channels & _CHANNELS[name])
-        lay[name] = at if held else None
-        at += count * slots0 if held else 0
-        lay["planes"] += count if held else 0
-    lay["words"] = at
+    held = [(name, name == "hits" or bool(channels & _CHANNELS[name]), count * PER_TILE) for name, count in _PLANES]
+    lay = _parts.section_offsets(frame_tiles(width, height), part_count, PER_TILE, held)
+    lay["planes"] = sum(words // PER_TILE for _, has, words in held if has)
     return lay
-
-
-def _part_slots(n_tiles: int, part: tuple[int, int]) -> np.ndarray:
-    """The whole image's slots that part (r, N) owns, in the part's own slot order."""
-    tiles = np.arange(part[0], n_tiles, part[1], dtype=np.int64)
-    return (tiles[:, None] * PER_TILE + np.arange(PER_TILE, dtype=np.int64)[None, :]).ravel()
 
 
 @dataclass
@@ -146,24 +133,9 @@ class AovState:
         the field when the states differ in version, channels, size, samples, seed or world_fingerprint, when a
         part is missing or comes twice, and when slots, tiles or an array does not fit the part."""
         states = list(states)
-        if not states:
-            raise ValueError("merge needs at least one state")
-        first = states[0]
-        for s in states[1:]:
-            for n in ("version", "channels", "width", "height", "part_count", "reserved", "seed", "world_fingerprint", "samples"):
-                if int(getattr(s, n)) != int(getattr(first, n)):
-                    raise ValueError(f"the states are not parts of one frame: {n} differs")
-        count = max(1, int(first.part_count))
-        by_part = {}
-        for s in states:
-            if int(s.part_index) in by_part:
-                raise ValueError(f"part_index {int(s.part_index)} comes twice")
-            by_part[int(s.part_index)] = s
-        for r in range(count):
-            if r not in by_part:
-                raise ValueError(f"part_index {r} of part_count {count} is missing")
-        if len(by_part) != count:
-            raise ValueError(f"part_index outside 0 .. part_count - 1 ({count})")
+        by_part = _parts.parts_in_order(states, ("version", "channels", "width", "height", "part_count", "reserved", "seed",
+                                                 "world_fingerprint", "samples"))
+        first, count = states[0], len(by_part)
         n_tiles = frame_tiles(int(first.width), int(first.height))
         slots = n_tiles * PER_TILE
         head = first.header()
@@ -174,7 +146,7 @@ class AovState:
                 setattr(whole, name, np.zeros(whole._shape(name), np.float32))
         for r in range(count):
             s = by_part[r]
-            at = _part_slots(n_tiles, (r, count))
+            at = _parts.part_slots(n_tiles, PER_TILE, (r, count))
             if int(s.slots) != at.size:
                 raise ValueError(f"part {r}: slots differs from the partition's ({at.size})")
             if int(s.tiles) != at.size // PER_TILE:
@@ -201,7 +173,7 @@ class AovState:
         self._check_arrays()
         out = []
         for r in range(part_count):
-            at = _part_slots(n_tiles, (r, part_count))
+            at = _parts.part_slots(n_tiles, PER_TILE, (r, part_count))
             head = self.header()
             head.update(part_index=r, part_count=part_count, slots=int(at.size), tiles=int(at.size) // PER_TILE)
             out.append(AovState(**head, **{name: np.ascontiguousarray(getattr(self, name)[..., at])
@@ -214,21 +186,11 @@ class AovState:
         self._check_arrays()
         count = max(1, int(self.part_count))
         lay = record_layout(int(self.width), int(self.height), int(self.channels), count)
-        words = lay["words"] if stride_bytes is None else stride_bytes // 4
-        if words < lay["words"] or (stride_bytes or 0) % 4:
-            raise ValueError("stride_bytes must be a multiple of 4 and at least the record's bytes")
-        rec = np.zeros(words, np.uint32)
-        rec[:RECORD_HEADER_WORDS] = (RECORD_VERSION, int(self.channels), int(self.part_index), count, int(self.samples),
-                                     int(self.slots), int(self.tiles), RECORD_MAGIC)
-        for name, planes in _PLANES:
-            a = getattr(self, name)
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a).view(np.uint32).reshape(planes, -1)
-            for k in range(planes):
-                at = lay[name] + k * lay["slots0"]
-                rec[at: at + a.shape[1]] = a[k]
-        return rec
+        header = (RECORD_VERSION, int(self.channels), int(self.part_index), count, int(self.samples), int(self.slots),
+                  int(self.tiles), RECORD_MAGIC)
+        planes = [(lay[name] + k * lay["slots0"], np.asarray(getattr(self, name)).reshape(count_, -1)[k])
+                  for name, count_ in _PLANES if getattr(self, name) is not None for k in range(count_)]
+        return _parts.pack_record(header, lay["words"], stride_bytes, planes)
 
 
 assert list(_HEADER) == [f for f in AovState.__dataclass_fields__][:len(_HEADER)]

@@ -16,8 +16,7 @@ struct rtw_rng {
     rtw_xoro s;
 };
 
-struct rtw_parts_layout;      // include/rtw_parts.h
-struct rtw_aov_parts_layout;  // include/rtw_aov_parts.h
+struct rtw_parts_layout;  // include/rtw_parts.h
 
 namespace rtw {
 
@@ -43,22 +42,15 @@ int sah_build_split(const float* lo, const float* hi, const float* tri, const fl
                     std::vector<rtw_bvh_node>& nodes, std::vector<float>& km, int32_t* root, int* depth,
                     int depth_cap = 0);
 
-// The pack and merge launches of rtw_accum_pack / rtw_accum_merge_parts (rtw_parts.hip; the layout is
-// include/rtw_parts.h's).  Pointers the layout's flags do not call for are null.  The callers have validated
-// the sizes: the launches only choose the 16-byte or the dword path.
-hipError_t parts_pack_launch(const rtw_parts_layout& L, int32_t part_index, uint32_t samples, const float* sums,
-                             const float* squares, const uint32_t* kept, const uint32_t* stop, void* d_packed,
-                             hipStream_t stream);
-hipError_t parts_merge_launch(const rtw_parts_layout& L, const void* d_gathered, uint64_t stride_bytes, float* sums,
-                              float* squares, uint32_t* kept, uint32_t* stop, hipStream_t stream);
-// fail() with the message of a refused merge: the field's name and the record (at[0]) and local tile (at[1])
-int parts_refuse(const char* field, const int32_t at[2]);
-// The same for rtw_aov_pack / rtw_aov_merge_parts (include/rtw_aov_parts.h).  planes: the accumulator's albedo,
-// normal and depth planes as held, one after the other, each the accumulator's own slots long; hits: its counts.
-hipError_t aov_parts_pack_launch(const rtw_aov_parts_layout& L, int32_t part_index, uint32_t samples, const float* planes,
-                                 const uint32_t* hits, void* d_packed, hipStream_t stream);
-hipError_t aov_parts_merge_launch(const rtw_aov_parts_layout& L, const void* d_gathered, uint64_t stride_bytes, float* planes,
-                                  uint32_t* hits, hipStream_t stream);
-int aov_parts_refuse(const char* field, int32_t record);
+// The pack and merge launches of rtw_accum_pack / rtw_accum_merge_parts and rtw_aov_pack / rtw_aov_merge_parts
+// (rtw_parts.hip; the layout is include/rtw_parts.h's).  arrays[s]: the accumulator's device array of the
+// layout's section s.  The callers have validated the sizes: the launches only choose the 16-byte or the dword path.
+hipError_t parts_pack_launch(const rtw_parts_layout& L, int32_t part_index, uint32_t samples, const void* const* arrays,
+                             void* d_packed, hipStream_t stream);
+hipError_t parts_merge_launch(const rtw_parts_layout& L, const void* d_gathered, uint64_t stride_bytes, void* const* arrays,
+                              hipStream_t stream);
+// fail() with the message of a refused merge of colour (tag 0) or AOV records (the layout's tag): the field's name,
+// the record (at[0]) and, for a stop, the local tile (at[1])
+int parts_refuse(uint32_t tag, const char* field, const int32_t at[2]);
 
 }  // namespace rtw

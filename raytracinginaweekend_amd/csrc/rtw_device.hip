@@ -6360,6 +6360,18 @@ extern "C" RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_
 }
 
 // ---- partition records (rtw.h; include/rtw_parts.h).  The kernels are rtw_parts.hip's. ----
+namespace {
+// a's device arrays in the order of its record's sections: sums, then what its flags call for
+struct accum_sections {
+    void* p[RTW_PARTS_MAX_SECTIONS];
+    explicit accum_sections(const rtw_accum* a) {
+        int n = 0;
+        for (void* q : {(void*)a->sums, (void*)a->squares, (void*)a->kept, (void*)a->tile_stop})
+            if (q) p[n++] = q;
+    }
+};
+}  // namespace
+
 extern "C" RTW_API int rtw_accum_pack(rtw_accum* a, void* d_packed, void* stream_) {
     if (!a || !d_packed) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
@@ -6371,8 +6383,7 @@ extern "C" RTW_API int rtw_accum_pack(rtw_accum* a, void* d_packed, void* stream
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
     int rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
-    HIP_TRY(rtw::parts_pack_launch(L, a->info.part_index, a->info.samples, a->sums, a->squares, a->kept, a->tile_stop, d_packed,
-                                   stream));
+    HIP_TRY(rtw::parts_pack_launch(L, a->info.part_index, a->info.samples, accum_sections(a).p, d_packed, stream));
     return accum_leave(a, stream);
 }
 
@@ -6387,10 +6398,10 @@ extern "C" RTW_API int rtw_accum_merge_parts(rtw_accum* whole, const void* d_gat
     const uint32_t flags = a->info.flags;
     int32_t at[2] = {0, 0};
     rtw_parts_layout L;
-    if (rtw_parts_layout_of(&a->p, flags, part_count, &L) != 0) return rtw::parts_refuse("params", at);
+    if (rtw_parts_layout_of(&a->p, flags, part_count, &L) != 0) return rtw::parts_refuse(0u, "params", at);
     if ((uint32_t)L.n_tiles != a->tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
     if (stride_bytes < (int64_t)(L.words * 4) || stride_bytes % 4 != 0 || ((uintptr_t)d_gathered & 3u) != 0)
-        return rtw::parts_refuse("stride_bytes", at);
+        return rtw::parts_refuse(L.tag, "stride_bytes", at);
     // The headers (and, adaptive, the stop sections) come back first, after the work already on `stream` (the
     // packs, or the collective that filled the buffer): everything is refused before anything is launched.
     HIP_TRY(hipSetDevice(a->g->device));
@@ -6405,25 +6416,14 @@ extern "C" RTW_API int rtw_accum_merge_parts(rtw_accum* whole, const void* d_gat
         uint32_t* h = host.data() + (size_t)r * own_words;
         HIP_TRY(hipMemcpyAsync(h, rec, RTW_PARTS_HEADER_WORDS * 4, hipMemcpyDeviceToHost, stream));
         if ((flags & RTW_ACCUM_ADAPTIVE) && L.tiles0 > 0)
-            HIP_TRY(hipMemcpyAsync(h + RTW_PARTS_HEADER_WORDS, rec + L.stop * 4, (size_t)L.tiles0 * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(h + RTW_PARTS_HEADER_WORDS, rec + L.at[L.stop] * 4, (size_t)L.tiles0 * 4, hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));
     uint32_t samples = 0;
-    for (int32_t r = 0; r < part_count; ++r) {
-        const uint32_t* h = host.data() + (size_t)r * own_words;
-        at[0] = r;
-        if (const char* bad = rtw_parts_check_header(&L, r, h)) return rtw::parts_refuse(bad, at);
-        const uint32_t s = h[RTW_PARTS_H_SAMPLES];
-        if (!(flags & RTW_ACCUM_ADAPTIVE) && r > 0 && s != samples) return rtw::parts_refuse("samples", at);
-        samples = std::max(samples, s);
-        if (flags & RTW_ACCUM_ADAPTIVE)
-            for (int32_t lt = 0; lt < rtw_parts_tiles(&L, r); ++lt) {
-                const uint32_t v = h[RTW_PARTS_HEADER_WORDS + lt];
-                at[1] = lt;
-                if (v == 1u || v > s) return rtw::parts_refuse("tile_stop", at);
-            }
-    }
-    HIP_TRY(rtw::parts_merge_launch(L, d_gathered, (uint64_t)stride_bytes, a->sums, a->squares, a->kept, a->tile_stop, stream));
+    const char* field = nullptr;
+    if (rtw_parts_check(&L, host.data(), own_words, RTW_PARTS_HEADER_WORDS, &samples, &field, at) != 0)
+        return rtw::parts_refuse(L.tag, field, at);
+    HIP_TRY(rtw::parts_merge_launch(L, d_gathered, (uint64_t)stride_bytes, accum_sections(a).p, stream));
     rc = accum_leave(a, stream);
     if (rc != RTW_OK) return rc;
     if (flags & RTW_ACCUM_ADAPTIVE) {  // the host's copy of the stop map and its zeros, as after an adapt
@@ -6759,15 +6759,25 @@ extern "C" RTW_API int rtw_aov_hits(rtw_aov* a, uint32_t* d_out, void* stream) {
 // ---- AOV partition records and state (rtw.h; include/rtw_aov_parts.h).  The kernels are rtw_parts.hip's. ----
 namespace {
 // the layout of the records of a's group, checked against a's own geometry
-int aov_layout(const rtw_aov* a, int32_t part_count, rtw_aov_parts_layout* L) {
+int aov_layout(const rtw_aov* a, int32_t part_count, rtw_parts_layout* L) {
+    const int32_t none[2] = {0, 0};
     rtw_render_params p;
     std::memset(&p, 0, sizeof(p));
     p.width = a->info.width;
     p.height = a->info.height;
-    if (rtw_aov_parts_layout_of(&p, a->info.channels, part_count, L) != 0) return rtw::aov_parts_refuse("params", 0);
+    if (rtw_aov_parts_layout_of(&p, a->info.channels, part_count, L) != 0) return rtw::parts_refuse(RTW_AOV_PARTS_MAGIC, "params", none);
     if ((uint32_t)L->n_tiles != a->n_tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad AOV accumulator geometry");
     return RTW_OK;
 }
+
+// a's device arrays in the order of its record's sections: the value planes, its own slots apart, then the hits
+struct aov_sections {
+    void* p[RTW_PARTS_MAX_SECTIONS];
+    aov_sections(const rtw_aov* a, const rtw_parts_layout& L) {
+        for (int32_t s = 0; s + 1 < L.sections; ++s) p[s] = a->planes ? a->planes + (size_t)s * a->slots : nullptr;
+        p[L.sections - 1] = a->hits;
+    }
+};
 
 void aov_state_info(const rtw_aov* a, rtw_aov_state_info* I) {
     std::memset(I, 0, sizeof(*I));
@@ -6804,12 +6814,12 @@ extern "C" RTW_API int rtw_aov_pack(rtw_aov* a, void* d_packed, void* stream) {
     if (!a || !d_packed) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
     if (((uintptr_t)d_packed & 3u) != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "d_packed must be 4-byte aligned");
-    rtw_aov_parts_layout L;
+    rtw_parts_layout L;
     const int rc = aov_layout(a, a->part_count, &L);
     if (rc != RTW_OK) return rc;
-    if ((uint32_t)rtw_aov_parts_tiles(&L, a->part_index) != a->tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad AOV accumulator geometry");
+    if ((uint32_t)rtw_parts_tiles(&L, a->part_index) != a->tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad AOV accumulator geometry");
     HIP_TRY(hipSetDevice(a->g->device));
-    HIP_TRY(rtw::aov_parts_pack_launch(L, a->part_index, a->info.samples, a->planes, a->hits, d_packed, (hipStream_t)stream));
+    HIP_TRY(rtw::parts_pack_launch(L, a->part_index, a->info.samples, aov_sections(a, L).p, d_packed, (hipStream_t)stream));
     return RTW_OK;
 }
 
@@ -6821,11 +6831,12 @@ extern "C" RTW_API int rtw_aov_merge_parts(rtw_aov* whole, const void* d_gathere
     if (a->part_index != 0 || a->part_count != 1)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "a merge fills the whole image's AOV accumulator: part_index / part_count is not 0 / 1");
     hipStream_t stream = (hipStream_t)stream_;
-    rtw_aov_parts_layout L;
+    rtw_parts_layout L;
     const int rc = aov_layout(a, part_count, &L);
     if (rc != RTW_OK) return rc;
+    int32_t at[2] = {0, 0};
     if (stride_bytes < (int64_t)(L.words * 4) || stride_bytes % 4 != 0 || ((uintptr_t)d_gathered & 3u) != 0)
-        return rtw::aov_parts_refuse("stride_bytes", 0);
+        return rtw::parts_refuse(L.tag, "stride_bytes", at);
     // The headers come back first, after the work already on `stream` (the packs, or the collective that filled
     // the buffer): everything is refused before anything is launched.
     HIP_TRY(hipSetDevice(a->g->device));
@@ -6836,9 +6847,8 @@ extern "C" RTW_API int rtw_aov_merge_parts(rtw_aov* whole, const void* d_gathere
     HIP_TRY(hipStreamSynchronize(stream));
     uint32_t samples = 0;
     const char* field = nullptr;
-    int32_t at = 0;
-    if (rtw_aov_parts_check(&L, host.data(), RTW_PARTS_HEADER_WORDS, &samples, &field, &at) != 0) return rtw::aov_parts_refuse(field, at);
-    HIP_TRY(rtw::aov_parts_merge_launch(L, d_gathered, (uint64_t)stride_bytes, a->planes, a->hits, stream));
+    if (rtw_parts_check(&L, host.data(), RTW_PARTS_HEADER_WORDS, 0, &samples, &field, at) != 0) return rtw::parts_refuse(L.tag, field, at);
+    HIP_TRY(rtw::parts_merge_launch(L, d_gathered, (uint64_t)stride_bytes, aov_sections(a, L).p, stream));
     a->info.samples = samples;
     return RTW_OK;
 }

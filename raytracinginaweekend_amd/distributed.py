@@ -19,6 +19,7 @@ rank 0 the whole image's accumulator, with its noise estimate, stop map, kept co
 
 DistributedAovAccumulator does the same for the first-hit AOV pass (aov.py, include/rtw_aov_parts.h): the denoiser's
 guide and albedo images are traced an N-th per rank and merged on rank 0, beside the colour accumulator's state.
+Both are one mechanism (_DistributedRecords): a record of another section table travels the same way.
 """
 from __future__ import annotations
 
@@ -172,7 +173,66 @@ def gather_records(record, gathered, rank: int, world_size: int) -> None:
         dist.gather(record, None, dst=0)
 
 
-class DistributedAccumulator:
+class _DistributedRecords:
+    """What the accumulators across ranks share: `local`, this rank's accumulator of part (rank, world_size); `whole`,
+    rank 0's of the whole image (world_size 1: the same one); the record, its stride and rank 0's gathered buffer;
+    `sync`.  `make(dworld, part)` builds an accumulator with `packed_bytes`, `pack_into`, `merge_parts` and
+    `release`, of `part` or, for None, of the whole image."""
+
+    def __init__(self, world: World | DeviceWorld, rank: int, world_size: int, device: int, make):
+        import torch
+
+        if not 0 <= rank < world_size:
+            raise ValueError("rank must be within 0 .. world_size - 1")
+        self.torch = torch
+        self.rank, self.world_size = rank, world_size
+        self.dev = torch.device("cuda", device)
+        self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
+        self.whole = make(self.dworld, None) if rank == 0 else None
+        if world_size == 1:
+            self.local = self.whole
+        else:
+            self.local = make(self.dworld, (rank, world_size))
+            # (a stride of whole 16 bytes: every record of the gathered buffer takes the merge's 16-byte path)
+            self.stride_bytes = -(-self.local.packed_bytes() // 16) * 16
+            self.record = torch.zeros(self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
+            self.gathered = (torch.zeros(world_size * self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
+                             if rank == 0 else None)
+        self.samples = 0
+
+    def release(self) -> None:
+        for a in {id(a): a for a in (self.local, self.whole) if a is not None}.values():
+            a.release()
+        self.local = self.whole = None
+
+    def _stream(self) -> int:
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _device_collectives(self) -> bool:
+        import torch.distributed as dist
+
+        return dist.get_backend() == "nccl"
+
+    def sync(self):
+        """Pack, one gather onto rank 0, merge: returns `whole` on rank 0 and None elsewhere.  Every rank calls it."""
+        if self.world_size == 1:
+            return self.whole
+        self.local.pack_into(self.record, self._stream())
+        if self._device_collectives():
+            gather_records(self.record, self.gathered, self.rank, self.world_size)
+        else:  # stage through the host on both sides
+            host = self.record.cpu()
+            staged = self.torch.zeros(self.gathered.numel(), dtype=self.torch.int32) if self.rank == 0 else None
+            gather_records(host, staged, self.rank, self.world_size)
+            if self.rank == 0:
+                self.gathered.copy_(staged)
+        if self.rank != 0:
+            return None
+        self.whole.merge_parts(self.gathered, self.stride_bytes, self.world_size, self._stream())
+        return self.whole
+
+
+class DistributedAccumulator(_DistributedRecords):
     """A progressive accumulator of one frame across the ranks of a process group (one process per GPU).
 
     Rank r owns an `Accumulator` of part (r, world_size) in LAYOUT_TILES (`local`); rank 0 also owns `whole`, a
@@ -190,46 +250,21 @@ class DistributedAccumulator:
     def __init__(self, world: World | DeviceWorld, size: Size2i, max_depth: int, rank: int = 0, world_size: int = 1,
                  device: int = 0, *, seed: int = DEFAULT_SEED, tile: tuple[int, int] = (8, 8), moments: bool = False,
                  adaptive: bool = False, finite: bool = False, render_mode: RenderMode = RenderMode.Default):
-        import torch
-
         from .progressive import Accumulator
 
-        if not 0 <= rank < world_size:
-            raise ValueError("rank must be within 0 .. world_size - 1")
-        self.torch = torch
-        self.rank, self.world_size = rank, world_size
-        self.dev = torch.device("cuda", device)
-        self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
         kw = dict(seed=seed, device=device, tile=tile, moments=moments, adaptive=adaptive, finite=finite)
-        self.whole = Accumulator(self.dworld, size, max_depth, render_mode, **kw) if rank == 0 else None
-        if world_size == 1:
-            self.local = self.whole
-        else:
-            self.local = Accumulator(self.dworld, size, max_depth, render_mode, part=(rank, world_size),
-                                     layout=N.LAYOUT_TILES, **kw)
-            # (a stride of whole 16 bytes: every record of the gathered buffer takes the merge's 16-byte path)
-            self.stride_bytes = -(-self.local.packed_bytes() // 16) * 16
-            self.record = torch.zeros(self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
-            self.gathered = (torch.zeros(world_size * self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
-                             if rank == 0 else None)
+
+        def make(dworld, part):
+            if part is None:
+                return Accumulator(dworld, size, max_depth, render_mode, **kw)
+            return Accumulator(dworld, size, max_depth, render_mode, part=part, layout=N.LAYOUT_TILES, **kw)
+
+        super().__init__(world, rank, world_size, device, make)
         tw, th = tile
         self.frame_tiles = -(-size.width // tw) * -(-size.height // th)
         self.adaptive = bool(adaptive)
-        self.samples = 0  # the group's frontier: the samples of the active tiles, as one GPU would count them
+        # (samples: the group's frontier, the samples of the active tiles, as one GPU would count them)
         self.active_tiles = self.frame_tiles
-
-    def release(self) -> None:
-        for a in {id(a): a for a in (self.local, self.whole) if a is not None}.values():
-            a.release()
-        self.local = self.whole = None
-
-    def _stream(self) -> int:
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
-
-    def _device_collectives(self) -> bool:
-        import torch.distributed as dist
-
-        return dist.get_backend() == "nccl"
 
     def add(self, n: int) -> None:
         """The next `n` samples of this rank's pixels (asynchronous; adaptive: of its active tiles).  Like one
@@ -256,26 +291,8 @@ class DistributedAccumulator:
         self.active_tiles = t
         return t, p
 
-    def sync(self):
-        """Pack, one gather onto rank 0, merge: returns `whole` on rank 0 and None elsewhere.  Every rank calls it."""
-        if self.world_size == 1:
-            return self.whole
-        self.local.pack_into(self.record, self._stream())
-        if self._device_collectives():
-            gather_records(self.record, self.gathered, self.rank, self.world_size)
-        else:  # stage through the host on both sides
-            host = self.record.cpu()
-            staged = self.torch.zeros(self.gathered.numel(), dtype=self.torch.int32) if self.rank == 0 else None
-            gather_records(host, staged, self.rank, self.world_size)
-            if self.rank == 0:
-                self.gathered.copy_(staged)
-        if self.rank != 0:
-            return None
-        self.whole.merge_parts(self.gathered, self.stride_bytes, self.world_size, self._stream())
-        return self.whole
 
-
-class DistributedAovAccumulator:
+class DistributedAovAccumulator(_DistributedRecords):
     """The first-hit AOV accumulator of one frame across the ranks of a process group (one process per GPU): the
     guide and albedo images of `DistributedAccumulator`'s denoised preview, traced an N-th per rank.
 
@@ -292,36 +309,12 @@ class DistributedAovAccumulator:
 
     def __init__(self, world: World | DeviceWorld, size: Size2i, rank: int = 0, world_size: int = 1, device: int = 0, *,
                  seed: int = DEFAULT_SEED, channels=("albedo", "normal", "depth")):
-        import torch
-
         from .aov import AovAccumulator
 
-        if not 0 <= rank < world_size:
-            raise ValueError("rank must be within 0 .. world_size - 1")
-        self.torch = torch
-        self.rank, self.world_size = rank, world_size
-        self.dev = torch.device("cuda", device)
-        self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
-        kw = dict(seed=seed, device=device, channels=channels)
-        self.whole = AovAccumulator(self.dworld, size, **kw) if rank == 0 else None
-        if world_size == 1:
-            self.local = self.whole
-        else:
-            self.local = AovAccumulator(self.dworld, size, part=(rank, world_size), **kw)
-            # (a stride of whole 16 bytes: every record of the gathered buffer takes the merge's 16-byte path)
-            self.stride_bytes = -(-self.local.packed_bytes() // 16) * 16
-            self.record = torch.zeros(self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
-            self.gathered = (torch.zeros(world_size * self.stride_bytes // 4, dtype=torch.int32, device=self.dev)
-                             if rank == 0 else None)
-        self.samples = 0
+        def make(dworld, part):
+            return AovAccumulator(dworld, size, seed=seed, device=device, channels=channels, part=part or (0, 1))
 
-    def release(self) -> None:
-        for a in {id(a): a for a in (self.local, self.whole) if a is not None}.values():
-            a.release()
-        self.local = self.whole = None
-
-    def _stream(self) -> int:
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
+        super().__init__(world, rank, world_size, device, make)
 
     def add(self, n: int) -> None:
         """The next `n` camera samples of this rank's pixels (asynchronous)."""
@@ -329,26 +322,6 @@ class DistributedAovAccumulator:
             raise ValueError("n must be >= 0")
         self.local.add(n, self._stream())
         self.samples += n
-
-    def sync(self):
-        """Pack, one gather onto rank 0, merge: returns `whole` on rank 0 and None elsewhere.  Every rank calls it."""
-        import torch.distributed as dist
-
-        if self.world_size == 1:
-            return self.whole
-        self.local.pack_into(self.record, self._stream())
-        if dist.get_backend() == "nccl":
-            gather_records(self.record, self.gathered, self.rank, self.world_size)
-        else:  # stage through the host on both sides
-            host = self.record.cpu()
-            staged = self.torch.zeros(self.gathered.numel(), dtype=self.torch.int32) if self.rank == 0 else None
-            gather_records(host, staged, self.rank, self.world_size)
-            if self.rank == 0:
-                self.gathered.copy_(staged)
-        if self.rank != 0:
-            return None
-        self.whole.merge_parts(self.gathered, self.stride_bytes, self.world_size, self._stream())
-        return self.whole
 
 
 def render_adaptive_distributed(world: World | DeviceWorld, size: Size2i, max_depth: int, rank: int, world_size: int,

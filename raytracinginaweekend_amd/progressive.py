@@ -40,6 +40,7 @@ from dataclasses import dataclass, fields
 import numpy as np
 
 from . import _native as N
+from . import _parts
 from ._native import check, lib
 from .aov import AovAccumulator
 from .rendering import DEFAULT_SEED, DeviceWorld, RenderMode, Size2i, render_params
@@ -53,8 +54,8 @@ _HEADER = {**{n: np.uint32 for n in _U32}, **{n: np.int32 for n in _I32}, **{n: 
            **{n: np.int64 for n in _I64}}
 
 
-RECORD_VERSION = 1  # RTW_PARTS_VERSION
-RECORD_HEADER_WORDS = 8
+RECORD_VERSION = _parts.VERSION  # RTW_PARTS_VERSION
+RECORD_HEADER_WORDS = _parts.HEADER_WORDS
 
 
 def record_layout(width: int, height: int, tile: tuple[int, int], flags: int, part_count: int) -> dict:
@@ -62,24 +63,11 @@ def record_layout(width: int, height: int, tile: tuple[int, int], flags: int, pa
     offsets sums / squares / kept / stop (None: the flags do not call for the section) and words."""
     tw, th = tile
     per_tile = tw * th
-    n_tiles = -(-width // tw) * -(-height // th)
-    tiles0 = -(-n_tiles // part_count)
-    slots0 = tiles0 * per_tile
-    at = RECORD_HEADER_WORDS
-    lay = {"per_tile": per_tile, "n_tiles": n_tiles, "tiles0": tiles0, "slots0": slots0, "sums": at}
-    at += 3 * slots0
-    for name, flag, words in (("squares", N.ACCUM_MOMENTS, 3 * slots0), ("kept", N.ACCUM_FINITE, slots0),
-                              ("stop", N.ACCUM_ADAPTIVE, tiles0)):
-        lay[name] = at if flags & flag else None
-        at += words if flags & flag else 0
-    lay["words"] = at
+    lay = _parts.section_offsets(-(-width // tw) * -(-height // th), part_count, per_tile,
+                                 (("sums", True, 3 * per_tile), ("squares", flags & N.ACCUM_MOMENTS, 3 * per_tile),
+                                  ("kept", flags & N.ACCUM_FINITE, per_tile), ("stop", flags & N.ACCUM_ADAPTIVE, 1)))
+    lay["per_tile"] = per_tile
     return lay
-
-
-def _part_slots(n_tiles: int, per_tile: int, part: tuple[int, int]) -> tuple[np.ndarray, np.ndarray]:
-    """(the frame's tiles part (r, N) owns, the whole image's slots they are)."""
-    tiles = np.arange(part[0], n_tiles, part[1], dtype=np.int64)
-    return tiles, (tiles[:, None] * per_tile + np.arange(per_tile, dtype=np.int64)[None, :]).ravel()
 
 
 @dataclass
@@ -189,25 +177,9 @@ class AccumState:
         samples differ between parts that are not adaptive.  Adaptive: samples is the largest of the parts' (a
         part whose tiles have all stopped no longer counts, `Accumulator.add`)."""
         states = list(states)
-        if not states:
-            raise ValueError("merge needs at least one state")
-        first = states[0]
-        for s in states[1:]:
-            for n in ("version", "flags", "width", "height", "tile_width", "tile_height", "part_count", "max_depth",
-                      "render_mode", "reserved", "seed", "world_fingerprint"):
-                if int(getattr(s, n)) != int(getattr(first, n)):
-                    raise ValueError(f"the states are not parts of one frame: {n} differs")
-        count = max(1, int(first.part_count))
-        by_part = {}
-        for s in states:
-            if int(s.part_index) in by_part:
-                raise ValueError(f"part_index {int(s.part_index)} comes twice")
-            by_part[int(s.part_index)] = s
-        for r in range(count):
-            if r not in by_part:
-                raise ValueError(f"part_index {r} of part_count {count} is missing")
-        if len(by_part) != count:
-            raise ValueError(f"part_index outside 0 .. part_count - 1 ({count})")
+        by_part = _parts.parts_in_order(states, ("version", "flags", "width", "height", "tile_width", "tile_height", "part_count",
+                                                 "max_depth", "render_mode", "reserved", "seed", "world_fingerprint"))
+        first, count = states[0], len(by_part)
         flags = int(first.flags)
         adaptive = bool(flags & N.ACCUM_ADAPTIVE)
         per_tile, n_tiles = int(first.tile_width) * int(first.tile_height), first._frame_tiles()
@@ -219,7 +191,7 @@ class AccumState:
         samples = int(first.samples)
         for r in range(count):
             s = by_part[r]
-            tiles, at = _part_slots(n_tiles, per_tile, (r, count))
+            tiles, at = _parts.part_tiles(n_tiles, (r, count)), _parts.part_slots(n_tiles, per_tile, (r, count))
             if int(s.slots) != at.size:
                 raise ValueError(f"part {r}: slots differs from the partition's ({at.size})")
             if not adaptive and int(s.samples) != samples:
@@ -263,7 +235,7 @@ class AccumState:
                              "holds such a state, and its parts could not tell")
         out = []
         for r in range(part_count):
-            tiles, at = _part_slots(n_tiles, per_tile, (r, part_count))
+            tiles, at = _parts.part_tiles(n_tiles, (r, part_count)), _parts.part_slots(n_tiles, per_tile, (r, part_count))
             stop = None if self.tile_stop is None else np.ascontiguousarray(self.tile_stop[tiles])
             samples = int(self.samples)
             if stop is not None and not (stop == 0).any():
@@ -280,19 +252,12 @@ class AccumState:
         with zeros to `stride_bytes`: what a rank without device-aware collectives sends."""
         count = max(1, int(self.part_count))
         lay = record_layout(int(self.width), int(self.height), (int(self.tile_width), int(self.tile_height)), int(self.flags), count)
-        words = lay["words"] if stride_bytes is None else stride_bytes // 4
-        if words < lay["words"] or (stride_bytes or 0) % 4:
-            raise ValueError("stride_bytes must be a multiple of 4 and at least the record's bytes")
-        rec = np.zeros(words, np.uint32)
-        rec[:RECORD_HEADER_WORDS] = (RECORD_VERSION, int(self.flags), int(self.part_index), count, int(self.samples),
-                                     int(self.slots), self.tiles, 0)
-        for name, arr in (("sums", self.sums), ("squares", self.squares), ("kept", self.kept), ("stop", self.tile_stop)):
+        sections = (("sums", self.sums), ("squares", self.squares), ("kept", self.kept), ("stop", self.tile_stop))
+        for name, arr in sections:
             if (arr is None) != (lay[name] is None):
                 raise ValueError(f"{name} does not go with the flags")
-            if arr is not None:
-                flat = np.ascontiguousarray(arr).view(np.uint32).ravel()
-                rec[lay[name]: lay[name] + flat.size] = flat
-        return rec
+        header = (RECORD_VERSION, int(self.flags), int(self.part_index), count, int(self.samples), int(self.slots), self.tiles, 0)
+        return _parts.pack_record(header, lay["words"], stride_bytes, [(lay[name], arr) for name, arr in sections if arr is not None])
 
 
 assert [f.name for f in fields(AccumState)][:len(_HEADER)] == [n for n, _ in N.AccumInfo._fields_]

@@ -4,7 +4,7 @@ Merging the AOV accumulators of parts (0..N-1, N) is a placement of 64-slot tile
 everything is checked bit for bit on synthetic states that hold what a value-level copy would damage: random u32
 patterns as planes (NaN payloads, -0), hit counts up to the sample count, zeros in padding slots.  The numpy pair
 `AovState.merge` / `split`, numpy-packed records through the host twin `rtw_aov_merge_parts_host`, a gloo gather of
-such records onto rank 0, and the stand-alone program tests/native/aov_parts_check.c (the shared header alone,
+such records onto rank 0, and the stand-alone program tests/native/parts_check.c (the shared headers alone,
 built plain and with -fsanitize=address,undefined, run alone) must all reproduce the unsplit state.  37 x 19 has
 15 tiles with edge tiles on both axes, 16 x 8 has 2; with 16 parts at least one part holds no tiles."""
 import ctypes as C
@@ -247,12 +247,12 @@ def test_state_checkpoint_roundtrip_and_repartition(tmp_path):
 
 def test_header_compiles_as_c99():
     src = ('#include "rtw_aov_parts.h"\n'
-           "int main(void){rtw_aov* a = 0; rtw_aov_state_info i; rtw_render_params p = {0}; rtw_aov_parts_layout L; int64_t b;\n"
-           "uint32_t n; const char* f; int32_t at;\n"
+           "int main(void){rtw_aov* a = 0; rtw_aov_state_info i; rtw_render_params p = {0}; rtw_parts_layout L; int64_t b;\n"
+           "uint32_t n; const char* f; int32_t at[2]; uint32_t* dst[RTW_PARTS_MAX_SECTIONS] = {0};\n"
            "return rtw_aov_create_part(0, &p, RTW_AOV_ALBEDO, &a) + rtw_aov_packed_bytes(&p, 7u, 2, &b) + rtw_aov_pack(a, 0, 0)\n"
            "+ rtw_aov_merge_parts(a, 0, 0, 1, 0) + rtw_aov_merge_parts_host(&p, 7u, 0, 0, 1, 0, 0, 0, 0, &n)\n"
            "+ rtw_aov_get_state_info(a, &i) + rtw_aov_export_state(a, 0, 0, 0, 0) + rtw_aov_import_state(a, &i, 0, 0, 0, 0)\n"
-           "+ rtw_aov_parts_layout_of(&p, 7u, 2, &L) + rtw_aov_parts_merge(&p, 7u, 0, 0, 1, 0, 0, 0, 0, &n, &f, &at)\n"
+           "+ rtw_aov_parts_layout_of(&p, 7u, 2, &L) + rtw_parts_merge(&L, 0, 0, dst, &n, &f, at)\n"
            "+ (int)sizeof(rtw_aov_state_info);}\n")
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function", "-fsyntax-only", "-I",
                     os.path.join(ROOT, "include"), "-x", "c", "-"], input=src, text=True, check=True)
@@ -262,7 +262,7 @@ def test_header_compiles_as_c99():
 # ---- the stand-alone program: the shared header alone, plain and under the sanitizers -----------------------
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
-    src = os.path.join(ROOT, "tests", "native", "aov_parts_check.c")
+    src = os.path.join(ROOT, "tests", "native", "parts_check.c")
     d = tmp_path_factory.mktemp("aov_parts")
     plain, san = str(d / "aov_parts_check"), str(d / "aov_parts_check_san")
     subprocess.run(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function", "-o", plain, src, "-lm"],
@@ -290,7 +290,7 @@ def test_stand_alone_program_on_the_same_cases(programs, tmp_path, sanitized):
         with open(path, "wb") as f:
             f.write(struct.pack("<3iIQ", *size, n, channels, stride // 4))
             f.write(np.ascontiguousarray(gathered, np.uint32).tobytes())
-        out = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
+        out = subprocess.run([exe, "aov", path], capture_output=True, text=True, timeout=120)
         assert out.returncode == 0, (size, channels, n, out.stdout[-2000:], out.stderr[-2000:])
         return out.stdout.split("\n")
 

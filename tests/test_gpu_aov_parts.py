@@ -175,6 +175,25 @@ def test_both_copy_widths_and_untouched_padding(worlds):
     dw.release()
 
 
+def test_an_unaligned_gather_at_an_odd_stride(worlds):
+    """All channels (8 sections), 44 x 26, N = 3: the records packed into a view one word off 16 bytes and merged at
+    a stride of 4 mod 16 -- only alignment keeps them off the 16-byte path -- give the bits of the aligned run."""
+    size, n = R.Size2i(44, 26), 3
+    dw = R.DeviceWorld(worlds("final_scene1"), 0)
+    single = R.AovAccumulator(dw, size, seed=SEED)
+    parts = make_parts(dw, size, n)
+    for acc in parts + [single]:
+        acc.add(3)
+    aligned, odd = R.AovAccumulator(dw, size, seed=SEED), R.AovAccumulator(dw, size, seed=SEED)
+    buf, stride = pack_and_merge(parts, aligned)
+    assert buf.data_ptr() % 16 == 0 and stride % 16 == 0
+    buf, stride = pack_and_merge(parts, odd, pad_bytes=4, offset_words=1)
+    assert buf[1:].data_ptr() % 16 == 4 and stride % 16 == 4
+    same_state(aligned.state(), single.state(), "aligned")
+    same_state(odd.state(), aligned.state(), "one word off, stride 4 mod 16")
+    dw.release()
+
+
 # ---- 5. continue and re-partition -------------------------------------------------------------------------
 def test_continue_and_repartition(worlds, tmp_path):
     name = "earth_motion"

@@ -184,6 +184,71 @@ def test_adaptive_parts_take_the_single_decisions(worlds, huge_target):
     dw.release()
 
 
+# ---- 3b. every section of the colour record in one launch -----------------------------------------------------
+def test_mixed_section_widths_and_an_unaligned_gather(worlds):
+    """moments + finite + adaptive on the 8 x 8 tile, N = 3: sums, squares and kept go as 16-byte units beside the
+    dword stop map in one pack and one merge launch.  The same parts packed into a view one word off 16 bytes and
+    merged at a stride of 4 mod 16 take the dword path for every section: the same bits."""
+    import torch
+
+    world, size, depth, n, tile = worlds("final_scene1"), R.Size2i(44, 26), 10, 3, (8, 8)
+    kw = dict(moments=True, finite=True, adaptive=True)
+    dw = R.DeviceWorld(world, 0)
+    single = R.Accumulator(dw, size, depth, seed=SEED, **kw)
+    parts = make_parts(dw, size, depth, n, tile, **kw)
+    for acc in parts + [single]:
+        acc.add(8)
+    st = single.state()
+    target = float(f32(np.median(F.tiles_E(st.sums, st.squares, st.kept, size, tile, (0, 1)))))
+    for acc in parts + [single]:
+        acc.adapt(target, 8)
+        acc.add(4)
+    want = single.state()
+    assert (want.tile_stop == 8).any() and (want.tile_stop == 0).any()  # stopped and active tiles cross the merge
+    whole = R.Accumulator(dw, size, depth, seed=SEED, **kw)
+    pack_and_merge(parts, whole)
+    aligned = whole.state()
+    same_state(aligned, want, "16-byte sections beside the dword stop map")
+    assert (whole.kept_counts() == single.kept_counts()).all() and whole.samples == single.samples
+    # one word off, and a stride that is a multiple of 4 but not of 16
+    stride = parts[0].packed_bytes() + 4
+    assert parts[0].packed_bytes() % 16 == 0 and stride % 16 == 4
+    buf = torch.full((1 + n * stride // 4,), 0x5A5A5A5A, dtype=torch.int32, device="cuda:0")
+    gathered = buf[1:]
+    assert gathered.data_ptr() % 16 == 4
+    for r, p in enumerate(parts):
+        p.pack_into(gathered[r * stride // 4: (r + 1) * stride // 4])
+    again = R.Accumulator(dw, size, depth, seed=SEED, **kw)
+    again.merge_parts(gathered, stride, n)
+    same_state(again.state(), aligned, "unaligned gather")
+    host = buf.cpu().numpy().view(np.uint32)
+    assert host[0] == 0x5A5A5A5A
+    for r, p in enumerate(parts):  # the records word for word, and the word between them untouched
+        assert (host[1 + r * stride // 4: 1 + (r + 1) * stride // 4] == np.append(p.state().packed(), np.uint32(0x5A5A5A5A))).all(), r
+    dw.release()
+
+
+def test_more_parts_than_tiles(worlds):
+    """26 parts of the 24 tiles of 44 x 26: parts 24 and 25 pack a header and zeros, and the merge is the single
+    accumulator."""
+    world, size, depth, n, tile = worlds("final_scene1"), R.Size2i(44, 26), 5, 26, (8, 8)
+    kw = dict(moments=True, finite=True, adaptive=True)
+    dw = R.DeviceWorld(world, 0)
+    single = R.Accumulator(dw, size, depth, seed=SEED, **kw)
+    parts = make_parts(dw, size, depth, n, tile, **kw)
+    assert [p.tiles for p in parts] == [1] * 24 + [0] * 2
+    for acc in parts + [single]:
+        acc.add(3)
+    whole = R.Accumulator(dw, size, depth, seed=SEED, **kw)
+    gathered, stride = pack_and_merge(parts, whole)
+    host = gathered.cpu().numpy().view(np.uint32).reshape(n, -1)
+    for r in (24, 25):
+        assert tuple(host[r][:4]) == (1, single.state().flags, r, n) and tuple(host[r][5:8]) == (0, 0, 0)
+        assert (host[r][8:] == 0).all()
+    same_state(whole.state(), single.state(), "26 parts of 24 tiles")
+    dw.release()
+
+
 # ---- 4. continue and re-partition; 5. denoise through the merge ---------------------------------------------
 def test_continue_repartition_and_denoise(worlds):
     world, size, depth, tile = worlds("final_scene1"), R.Size2i(44, 26), 50, (8, 8)

@@ -257,7 +257,7 @@ def test_stand_alone_program_on_the_same_cases(programs, tmp_path, sanitized):
         with open(path, "wb") as f:
             f.write(struct.pack("<5iIQ", *size, *tile, n, flags, stride // 4))
             f.write(np.ascontiguousarray(gathered, np.uint32).tobytes())
-        out = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
+        out = subprocess.run([exe, "colour", path], capture_output=True, text=True, timeout=120)
         assert out.returncode == 0, (size, tile, flags, n, out.stdout[-2000:], out.stderr[-2000:])
         return out.stdout.split("\n")
 
