@@ -430,18 +430,30 @@ RTW_API int rtw_render_device(rtw_gpu_world* gw, const rtw_render_params* params
  * without it, nor for rtw_render*.  A finite accumulator always takes single-sample work items, as one with
  * moments does: the accumulate pass is where samples are seen one by one, so a whole-pixel launch cannot filter.
  * On a pixel with no rejected sample every output is the plain accumulator's, bit for bit.  Dropping samples
- * biases the estimate (the dropped paths carried energy): the exact reference image stays the plain accumulator's. */
+ * biases the estimate (the dropped paths carried energy): the exact reference image stays the plain accumulator's.
+ *
+ * Sample clamping (RTW_ACCUM_CLAMP, needs RTW_ACCUM_FINITE; include/rtw_clamp.h has the definition, DESIGN.md
+ * 5.5j).  The accumulator has a level L (f32, 0 < L < inf; rtw_accum_create_clamp).  The accumulate pass scales
+ * every finite sample whose largest channel exceeds L so that it equals L (the hue is kept, no accumulated channel
+ * exceeds L), and keeps, per slot, `clamped` (one uint32_t: the samples it scaled) and `lost` (three f32: the sum of
+ * what it took out of them).  Sums, squares and kept hold the clamped samples, so every resolve, the noise estimate
+ * and rtw_accum_adapt are the finite accumulator's on them; rtw_accum_resolve_clamp_loss gives lost / kept, the
+ * mean radiance the clamp removed from each pixel.  The flag combines with RTW_ACCUM_MOMENTS and
+ * RTW_ACCUM_ADAPTIVE.  Such an accumulator always takes single-sample work items, as a finite one does.  On a
+ * pixel with no clamped sample every value is the finite accumulator's, bit for bit.  Clamping biases the estimate
+ * (it removes energy): nothing changes for accumulators created without the flag, nor for rtw_render*. */
 typedef struct rtw_accum rtw_accum;
 #define RTW_ACCUM_MOMENTS 1u  /* also keep per-channel sums of squares (the noise estimate) */
 #define RTW_ACCUM_ADAPTIVE 2u /* per-tile stop map: converged tiles take no more samples */
 #define RTW_ACCUM_FINITE 4u   /* leave non-finite samples out of the sums; per-slot kept counts */
+#define RTW_ACCUM_CLAMP 8u    /* scale finite samples above the level down to it; per-slot clamped counts and lost */
 typedef struct rtw_accum_info { /* all fields fixed-width, no padding; also the checkpoint header */
     uint32_t version; /* 1 */
     uint32_t flags;   /* RTW_ACCUM_* */
     int32_t width, height, tile_width, tile_height, part_index, part_count;
     int32_t max_depth, render_mode;
     uint32_t samples;  /* samples added so far, per pixel */
-    uint32_t reserved; /* 0 */
+    uint32_t reserved; /* 0; with RTW_ACCUM_CLAMP the bits of the f32 level (an import of another level is refused) */
     uint64_t seed;
     uint64_t world_fingerprint; /* rtw_world_fingerprint of the uploaded world */
     int64_t slots;              /* floats per state array = 3 * slots */
@@ -453,6 +465,11 @@ typedef struct rtw_accum_info { /* all fields fixed-width, no padding; also the 
 RTW_API int rtw_world_fingerprint(const rtw_world* w, uint64_t* out);
 RTW_API int rtw_accum_create(rtw_gpu_world* gw, const rtw_render_params* params, uint32_t flags,
                              rtw_accum** out);
+/* An accumulator with RTW_ACCUM_CLAMP (flags must hold it and RTW_ACCUM_FINITE, else RTW_ERR_INVALID_ARGUMENT naming
+ * the flags) of clamp level `level`; a level that is NaN, <= 0 or infinite is refused with a message naming clamp.
+ * rtw_accum_create refuses the flag: it has no level.  Otherwise as rtw_accum_create. */
+RTW_API int rtw_accum_create_clamp(rtw_gpu_world* gw, const rtw_render_params* params, uint32_t flags, float level,
+                                   rtw_accum** out);
 RTW_API int rtw_accum_release(rtw_accum* a);
 /* Renders samples [samples, samples + n) of every slot and adds their colours to the running sums
  * in sample order (with RTW_ACCUM_MOMENTS also sq = sq + c * c per channel, product and sum each
@@ -526,6 +543,21 @@ RTW_API int rtw_accum_export_state(rtw_accum* a, float* host_sums, float* host_s
                                    uint32_t* host_kept);
 RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                    const float* host_squares, const uint32_t* host_tile_stop, const uint32_t* host_kept);
+/* RTW_ACCUM_CLAMP only (else RTW_ERR_INVALID_ARGUMENT).  rtw_accum_resolve_clamped: the clamped count of each pixel
+ * or slot, laid out and padded as rtw_accum_resolve_kept.  rtw_accum_resolve_clamp_loss: lost / (float)kept per
+ * channel (+0.0 for kept == 0), in the resolve's layout.  Asynchronous. */
+RTW_API int rtw_accum_resolve_clamped(rtw_accum* a, uint32_t* d_out, void* stream);
+RTW_API int rtw_accum_resolve_clamp_loss(rtw_accum* a, float* d_out, void* stream);
+/* The checkpoint of an accumulator with RTW_ACCUM_CLAMP: the four arrays of rtw_accum_export_state, under its
+ * must-be-non-null / must-be-NULL rule, plus clamped (one uint32_t per slot) and lost (3 * slots floats), both
+ * non-null.  The import also refuses an `info` whose level (reserved) differs, a clamped[slot] above kept[slot],
+ * and anything non-zero in a padding slot of clamped or lost, each with a message naming the field.  The three
+ * older pairs refuse an accumulator with RTW_ACCUM_CLAMP by name and are otherwise unchanged.  Synchronous. */
+RTW_API int rtw_accum_export_state_clamp(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_tile_stop,
+                                         uint32_t* host_kept, uint32_t* host_clamped, float* host_lost);
+RTW_API int rtw_accum_import_state_clamp(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                         const float* host_squares, const uint32_t* host_tile_stop,
+                                         const uint32_t* host_kept, const uint32_t* host_clamped, const float* host_lost);
 
 /* ---- partition records: accumulators across GPUs ------------------------------------------- */
 /* N accumulators of parts (0..N-1, N) of one frame, one per GPU, make the whole image's accumulator: each packs
@@ -537,10 +569,13 @@ RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info* info, con
  *
  * The record, in 4-byte words (include/rtw_parts.h has the arithmetic; S0 and T0 are the slots and tiles of part
  * (0, N), which owns the most tiles, so all N records have one size and one set of section offsets):
- *   header     8 words: record version (1), flags (RTW_ACCUM_*), part_index, part_count, samples, slots, tiles, 0
+ *   header     8 words: record version (1), flags (RTW_ACCUM_*), part_index, part_count, samples, slots, tiles, and
+ *                       0 or, with RTW_ACCUM_CLAMP, the bits of the f32 level
  *   sums       3 * S0 f32
  *   squares    3 * S0 f32   with RTW_ACCUM_MOMENTS
  *   kept       S0 u32       with RTW_ACCUM_FINITE
+ *   clamped    S0 u32       with RTW_ACCUM_CLAMP
+ *   lost       3 * S0 f32   with RTW_ACCUM_CLAMP
  *   tile_stop  T0 u32       with RTW_ACCUM_ADAPTIVE
  * A section's words past the partition's own slots or tiles are zero.
  *
@@ -556,7 +591,8 @@ RTW_API int rtw_accum_pack(rtw_accum* a, void* d_packed, void* stream);
  * part (0, 1).  First the headers are read back, after the work already on `stream` and after the calls already
  * issued on whole's world (the packs of its other accumulators, on any stream), and refused with a message
  * naming the field: stride_bytes; a record's version, flags (against whole's), part_index (record r holds part r),
- * part_count, slots and tiles (against the arithmetic), reserved; samples, which must be equal in all records
+ * part_count, slots and tiles (against the arithmetic), reserved (with RTW_ACCUM_CLAMP: clamp, the level against
+ * whole's); samples, which must be equal in all records
  * unless the flags hold RTW_ACCUM_ADAPTIVE.  With it whole's samples becomes the largest: rtw_accum_add does not
  * count when every tile of a part has stopped, so such a part's count stays where its last tile stopped, and the
  * largest is the count a single GPU would hold; its stop sections are read back too and a tile_stop of 1 or above
@@ -574,6 +610,13 @@ RTW_API int rtw_accum_merge_parts(rtw_accum* whole, const void* d_gathered, int6
 RTW_API int rtw_accum_merge_parts_host(const rtw_render_params* params, uint32_t flags, const void* gathered,
                                        int64_t stride_bytes, int32_t part_count, float* sums, float* squares,
                                        uint32_t* kept, uint32_t* tile_stop, uint32_t* samples);
+/* The same for records of accumulators with RTW_ACCUM_CLAMP (flags must hold it; rtw_accum_merge_parts_host refuses
+ * such flags by name): `level` is the whole's, a record of another level is refused naming clamp; clamped slots
+ * entries and lost 3 * slots floats of the whole image, both non-null. */
+RTW_API int rtw_accum_merge_parts_host_clamp(const rtw_render_params* params, uint32_t flags, float level,
+                                             const void* gathered, int64_t stride_bytes, int32_t part_count, float* sums,
+                                             float* squares, uint32_t* kept, uint32_t* clamped, float* lost,
+                                             uint32_t* tile_stop, uint32_t* samples);
 
 /* ---- first-hit AOVs ------------------------------------------------------------------------- */
 /* An AOV accumulator keeps, per pixel of the whole image, running sums of what the camera rays hit first:

@@ -18,7 +18,11 @@
  *   sums       3 * per_tile f32 a tile
  *   squares    3 * per_tile f32    with RTW_ACCUM_MOMENTS
  *   kept       per_tile u32        with RTW_ACCUM_FINITE
+ *   clamped    per_tile u32        with RTW_ACCUM_CLAMP
+ *   lost       3 * per_tile f32    with RTW_ACCUM_CLAMP
  *   tile_stop  1 u32               with RTW_ACCUM_ADAPTIVE (the layout's `stop` section)
+ * With RTW_ACCUM_CLAMP the header's last word of a colour record carries the bits of the accumulator's f32 level
+ * (the layout's `level`, set by rtw_parts_set_level; 0 without the flag), checked like every other header word.
  */
 #ifndef RTW_PARTS_H
 #define RTW_PARTS_H
@@ -54,6 +58,7 @@ typedef struct rtw_parts_layout {
     /* The section that is a stop map, one word a tile, or -1.  With one, the parts may differ in samples (the
      * whole's is the largest) and every stop must be 0 or within 2 .. its record's samples. */
     int32_t stop;
+    uint32_t level;    /* a colour record's last header word: 0, or the bits of the clamp level (RTW_ACCUM_CLAMP) */
     uint32_t per[RTW_PARTS_MAX_SECTIONS]; /* words of one tile */
     uint64_t at[RTW_PARTS_MAX_SECTIONS];  /* the section's first word in a record */
     uint64_t words;                       /* of a record */
@@ -78,6 +83,7 @@ RTW_HD int rtw_parts_frame(const rtw_render_params* params, int32_t part_count, 
     L->slots0 = (uint32_t)g.local_tiles * (uint32_t)L->per_tile;
     L->sections = 0;
     L->stop = -1;
+    L->level = 0u;
     L->words = RTW_PARTS_HEADER_WORDS;
     return 0;
 }
@@ -93,18 +99,30 @@ RTW_HD void rtw_parts_add_section(rtw_parts_layout* L, uint32_t per) {
 /* The layout of the colour records of `part_count` parts of params' frame.  0, or -1 for what rtw_parts_frame
  * refuses or unknown flags. */
 RTW_HD int rtw_parts_layout_of(const rtw_render_params* params, uint32_t flags, int32_t part_count, rtw_parts_layout* L) {
-    if ((flags & ~(RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE | RTW_ACCUM_FINITE)) || rtw_parts_frame(params, part_count, L) != 0) return -1;
+    if ((flags & ~(RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE | RTW_ACCUM_FINITE | RTW_ACCUM_CLAMP)) ||
+        ((flags & RTW_ACCUM_CLAMP) && !(flags & RTW_ACCUM_FINITE)) || rtw_parts_frame(params, part_count, L) != 0)
+        return -1;
     L->kind = flags;
     L->tag = 0u;
     rtw_parts_add_section(L, 3u * (uint32_t)L->per_tile);
     if (flags & RTW_ACCUM_MOMENTS) rtw_parts_add_section(L, 3u * (uint32_t)L->per_tile);
     if (flags & RTW_ACCUM_FINITE) rtw_parts_add_section(L, (uint32_t)L->per_tile);
+    if (flags & RTW_ACCUM_CLAMP) {
+        rtw_parts_add_section(L, (uint32_t)L->per_tile);
+        rtw_parts_add_section(L, 3u * (uint32_t)L->per_tile);
+    }
     if (flags & RTW_ACCUM_ADAPTIVE) {
         L->stop = L->sections;
         rtw_parts_add_section(L, 1u);
     }
     return 0;
 }
+
+/* the clamp level of a colour layout whose flags hold RTW_ACCUM_CLAMP (the records' last header word) */
+RTW_HD void rtw_parts_set_level(rtw_parts_layout* L, float level) { L->level = rtw_f2u(level); }
+
+/* a record's last header word: the AOV magic, or a colour record's level word */
+RTW_HD uint32_t rtw_parts_last_word(const rtw_parts_layout* L) { return L->tag != 0u ? L->tag : L->level; }
 
 /* the tiles part r owns: t = r, r + N, ... below n_tiles */
 RTW_HD int32_t rtw_parts_tiles(const rtw_parts_layout* L, int32_t r) {
@@ -125,7 +143,8 @@ RTW_HD uint64_t rtw_parts_source(uint64_t w, uint32_t per, uint32_t part_count, 
 RTW_HD int rtw_parts_wide(const rtw_parts_layout* L, int32_t s) { return L->per_tile % 4 == 0 && L->per[s] % 4 == 0; }
 
 /* A record's header against the layout: 0, or the name of the first field that differs.  A colour record:
- * "version", "flags", "part_index", "part_count", "slots", "tiles", "reserved"; an AOV record: "version", "magic",
+ * "version", "flags", "part_index", "part_count", "slots", "tiles", "reserved" (flags with RTW_ACCUM_CLAMP: "clamp",
+ * a level other than the layout's); an AOV record: "version", "magic",
  * "channels", "part_index", "part_count", "slots", "tiles".  samples is rtw_parts_check's to compare. */
 RTW_HD const char* rtw_parts_check_header(const rtw_parts_layout* L, int32_t r, const uint32_t* h) {
     const uint32_t tiles = (uint32_t)rtw_parts_tiles(L, r);
@@ -136,7 +155,7 @@ RTW_HD const char* rtw_parts_check_header(const rtw_parts_layout* L, int32_t r, 
     if (h[RTW_PARTS_H_PART_COUNT] != (uint32_t)L->part_count) return "part_count";
     if (h[RTW_PARTS_H_SLOTS] != tiles * (uint32_t)L->per_tile) return "slots";
     if (h[RTW_PARTS_H_TILES] != tiles) return "tiles";
-    if (L->tag == 0u && h[RTW_PARTS_H_TAG] != 0u) return "reserved";
+    if (L->tag == 0u && h[RTW_PARTS_H_TAG] != L->level) return (L->kind & RTW_ACCUM_CLAMP) ? "clamp" : "reserved";
     return (const char*)0;
 }
 

@@ -12,6 +12,7 @@ from .progressive import (
     Accumulator,
     AccumState,
     render_adaptive,
+    render_clamped,
     render_finite,
     render_progressive,
     render_to_noise,
@@ -68,6 +69,7 @@ __all__ = [
     "render_aov",
     "render_devices",
     "render_adaptive",
+    "render_clamped",
     "render_finite",
     "render_params",
     "render_progressive",

@@ -193,6 +193,7 @@ class RenderStats(C.Structure):
 ACCUM_MOMENTS = 1  # RTW_ACCUM_MOMENTS
 ACCUM_ADAPTIVE = 2  # RTW_ACCUM_ADAPTIVE
 ACCUM_FINITE = 4  # RTW_ACCUM_FINITE
+ACCUM_CLAMP = 8  # RTW_ACCUM_CLAMP
 
 
 class AccumInfo(C.Structure):  # rtw_accum_info: fixed-width fields, no padding (also the checkpoint header)
@@ -361,6 +362,21 @@ _SIGS = {
     "rtw_accum_merge_parts_host": (C.c_int, [C.POINTER(RenderParams), C.c_uint32, _P, C.c_int64, C.c_int32,
                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rtw_accum_create_clamp": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, C.POINTER(_P)]),
+    "rtw_accum_resolve_clamped": (C.c_int, [_P, _P, _P]),
+    "rtw_accum_resolve_clamp_loss": (C.c_int, [_P, _P, _P]),
+    "rtw_accum_export_state_clamp": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "rtw_accum_import_state_clamp": (C.c_int, [_P, C.POINTER(AccumInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_float)]),
+    "rtw_accum_merge_parts_host_clamp": (C.c_int, [C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, C.c_int64, C.c_int32,
+                                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_uint32)]),
+    "rtw_clamp_accumulate_host": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_float)]),
     "rtw_finite_accumulate_host":(C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtw_adapt_tiles_finite_host": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),

@@ -37,6 +37,7 @@
 #include "../../include/rtw_beam.h"
 #include "../../include/rtw_adapt.h"
 #include "../../include/rtw_finite.h"
+#include "../../include/rtw_clamp.h"
 #include "../../include/rtw_parts.h"
 #include "../../include/rtw_aov_parts.h"
 #include "rtw_common.h"
@@ -3406,6 +3407,56 @@ __global__ void accumulate_finite_kernel(const float* __restrict__ colors, uint3
     }
     kept[slot] = k;
 }
+// An accumulator's add with RTW_ACCUM_CLAMP (rtw_clamp.h): accumulate_finite_kernel's pass, and a finite sample whose
+// largest channel exceeds `level` is scaled down to it first; what the scaling took goes to lost and the sample is
+// counted in clamped.  One slot per lane; sum, sq, lost, kept and clamped stay in registers over the launch's
+// samples, so each state array takes one read and one write per launch.  The rejection and the clamp are branches,
+// as the rejection is above.  Stopped tiles are skipped.
+template <bool MOMENTS>
+__global__ void accumulate_clamp_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G, float level,
+                                        float* __restrict__ sums, float* __restrict__ squares, uint32_t* __restrict__ kept,
+                                        uint32_t* __restrict__ clamped, float* __restrict__ lost,
+                                        const uint32_t* __restrict__ tile_stop) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    if (!slot_pixel(G, slot, px, py)) return;
+    if (tile_stop && tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)] != 0) return;
+    float* S = sums + 3 * (size_t)slot;
+    float* Q = MOMENTS ? squares + 3 * (size_t)slot : nullptr;
+    float* D = lost + 3 * (size_t)slot;
+    V3 sum = v3(S[0], S[1], S[2]), sq = v3(0.0f, 0.0f, 0.0f), gone = v3(D[0], D[1], D[2]);
+    if (MOMENTS) sq = v3(Q[0], Q[1], Q[2]);
+    uint32_t k = kept[slot], n = clamped[slot];
+    const float* c = colors + 3 * (size_t)slot;
+    for (uint32_t s = 0; s < n_samples; ++s, c += 3 * (size_t)G.total) {
+        V3 col = v3(c[0], c[1], c[2]);
+        if (!rtw_finite_sample(col.x, col.y, col.z)) continue;
+        const float m = rtw_clamp_max(rtw_clamp_max(col.x, col.y), col.z);
+        if (m > level) {
+            const float f = level / m;
+            const V3 cut = v3(rtw_clamp_min(col.x * f, level), rtw_clamp_min(col.y * f, level), rtw_clamp_min(col.z * f, level));
+            gone = add(gone, v3(col.x - cut.x, col.y - cut.y, col.z - cut.z));
+            col = cut;
+            ++n;
+        }
+        sum = add(sum, col);
+        if (MOMENTS) sq = add(sq, conv(col, col));
+        ++k;
+    }
+    S[0] = sum.x;
+    S[1] = sum.y;
+    S[2] = sum.z;
+    if (MOMENTS) {
+        Q[0] = sq.x;
+        Q[1] = sq.y;
+        Q[2] = sq.z;
+    }
+    D[0] = gone.x;
+    D[1] = gone.y;
+    D[2] = gone.z;
+    kept[slot] = k;
+    clamped[slot] = n;
+}
 // the standard error of a channel's mean from its sum and sum of squares (rtw.h: the order is the contract;
 // the arithmetic is rtw_adapt.h's, shared with the host)
 __device__ __forceinline__ float accum_se(float sum, float sq, uint32_t samples, float& mean) {
@@ -3522,6 +3573,30 @@ __global__ void accum_resolve_finite_kernel(const float* __restrict__ sums, cons
     o[0] = r.x;
     o[1] = r.y;
     o[2] = r.z;
+}
+// The two resolves of an accumulator with RTW_ACCUM_CLAMP (a kernel of its own, as above).  what 4: clamped itself,
+// laid out and padded as kept is above; 5: lost / (float)kept per channel, +0 for kept == 0 (rtw_clamp_loss_mean).
+__global__ void accum_resolve_clamp_kernel(const float* __restrict__ lost, const uint32_t* __restrict__ kept,
+                                           const uint32_t* __restrict__ clamped, SlotGeom G, int what, float* out, int layout) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    const bool owned = slot_pixel(G, slot, px, py);
+    if (what == 4) {
+        uint32_t* o = (uint32_t*)out;
+        if (layout == RTW_LAYOUT_TILES) {
+            if (slot < G.total) o[slot] = owned ? clamped[slot] : 0u;
+        } else if (owned) {
+            o[(size_t)py * G.width + px] = clamped[slot];
+        }
+        return;
+    }
+    if (!owned) return;
+    const uint32_t n = kept[slot];
+    const float* D = lost + 3 * (size_t)slot;
+    float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
+    o[0] = rtw_clamp_loss_mean(D[0], n);
+    o[1] = rtw_clamp_loss_mean(D[1], n);
+    o[2] = rtw_clamp_loss_mean(D[2], n);
 }
 // accum_noise_kernel with each pixel's own kept as its n (the same fixed tree order)
 __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_finite_kernel(const float* __restrict__ sums,
@@ -5627,6 +5702,10 @@ struct AccumRun {
     uint32_t* active_perm = nullptr;
     uint32_t active = 0;
     uint32_t* kept = nullptr;  // RTW_ACCUM_FINITE: the per-slot kept counts (else null)
+    // RTW_ACCUM_CLAMP: the per-slot clamped counts, lost sums and the level (else null / 0)
+    uint32_t* clamped = nullptr;
+    float* lost = nullptr;
+    float level = 0.0f;
 };
 int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStream_t stream,
                       std::vector<uint64_t>* launch_items, const AccumRun* acc, bool acc_allow_wp = true);
@@ -5802,6 +5881,16 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         const unsigned blocks = (A.total + 255) / 256;
         if (A.whole_pixel) {
             // the render kernel wrote the pixels
+        } else if (acc && acc->clamped) {
+            const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
+            if (acc->squares)
+                hipLaunchKernelGGL(accumulate_clamp_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
+                                   s1 - s0, G, acc->level, acc->sums, acc->squares, acc->kept, acc->clamped, acc->lost,
+                                   acc->tile_stop);
+            else
+                hipLaunchKernelGGL(accumulate_clamp_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
+                                   s1 - s0, G, acc->level, acc->sums, (float*)nullptr, acc->kept, acc->clamped, acc->lost,
+                                   acc->tile_stop);
         } else if (acc && acc->kept) {
             const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
             if (acc->squares)
@@ -5886,6 +5975,10 @@ struct rtw_accum {
     float* sums = nullptr;     // 3 floats per slot, owned; padding slots stay zero
     float* squares = nullptr;  // the same with RTW_ACCUM_MOMENTS, else null
     uint32_t* kept = nullptr;  // RTW_ACCUM_FINITE: one count per slot (padding slots stay zero), else null
+    // RTW_ACCUM_CLAMP: one clamped count and three lost floats per slot (padding slots stay zero), else null; the level
+    uint32_t* clamped = nullptr;
+    float* lost = nullptr;
+    float level = 0.0f;
     double* noise_sum = nullptr;  // rtw_accum_noise: per-block partials (device), grown on first use
     uint32_t* noise_cnt = nullptr;
     // RTW_ACCUM_ADAPTIVE: the stop map, the compacted tile order of the adds (tiles + 1
@@ -5902,6 +5995,8 @@ static void accum_orphan(rtw_accum* a) {
     if (a->sums) (void)hipFree(a->sums);
     if (a->squares) (void)hipFree(a->squares);
     if (a->kept) (void)hipFree(a->kept);
+    if (a->clamped) (void)hipFree(a->clamped);
+    if (a->lost) (void)hipFree(a->lost);
     if (a->noise_sum) (void)hipFree(a->noise_sum);
     if (a->noise_cnt) (void)hipFree(a->noise_cnt);
     if (a->tile_stop) (void)hipFree(a->tile_stop);
@@ -5909,6 +6004,8 @@ static void accum_orphan(rtw_accum* a) {
     a->tile_stop = a->active_perm = nullptr;
     a->sums = a->squares = nullptr;
     a->kept = nullptr;
+    a->clamped = nullptr;
+    a->lost = nullptr;
     a->noise_sum = nullptr;
     a->noise_cnt = nullptr;
     a->g = nullptr;
@@ -5948,13 +6045,18 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
     if (what == 1 && a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs samples >= 2");
     // (what == 2, the sample counts: any accumulator at any point; a fresh one holds 0 everywhere)
     if (what == 3 && !a->kept) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the kept counts need an accumulator with RTW_ACCUM_FINITE");
+    if (what >= 4 && !a->clamped)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the clamped counts and the clamp loss need an accumulator with RTW_ACCUM_CLAMP");
     KArgs A;
     int rc = accum_args(a, 1, A);
     if (rc != RTW_OK) return rc;
     if (A.total == 0) return RTW_OK;
     rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
-    if (a->kept && what != 2)  // a finite accumulator divides by the pixel's own kept
+    if (what >= 4)
+        hipLaunchKernelGGL(accum_resolve_clamp_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream, (const float*)a->lost,
+                           (const uint32_t*)a->kept, (const uint32_t*)a->clamped, accum_geom(A), what, d_out, A.layout);
+    else if (a->kept && what != 2)  // a finite accumulator divides by the pixel's own kept
         hipLaunchKernelGGL(accum_resolve_finite_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream,
                            (const float*)a->sums, (const float*)a->squares, (const uint32_t*)a->kept, accum_geom(A), what,
                            d_out, A.layout);
@@ -5967,9 +6069,13 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
 }
 }  // namespace
 
-extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t flags, rtw_accum** out) {
+// rtw_accum_create and rtw_accum_create_clamp: `level` is read with RTW_ACCUM_CLAMP only (the callers checked it)
+static int accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t flags, float level, rtw_accum** out) {
     if (!g || !p || !out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
-    if (flags & ~(RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE | RTW_ACCUM_FINITE)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown accumulator flags");
+    if (flags & ~(RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE | RTW_ACCUM_FINITE | RTW_ACCUM_CLAMP))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "unknown accumulator flags");
+    if ((flags & RTW_ACCUM_CLAMP) && !(flags & RTW_ACCUM_FINITE))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "RTW_ACCUM_CLAMP needs RTW_ACCUM_FINITE (the clamp sees finite samples only, and its loss is a mean over kept)");
     if ((flags & RTW_ACCUM_ADAPTIVE) && !(flags & RTW_ACCUM_MOMENTS))
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "RTW_ACCUM_ADAPTIVE needs RTW_ACCUM_MOMENTS (the stop test reads the squares)");
     if (p->thread_count > 1)
@@ -5999,7 +6105,8 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     I.max_depth = p->max_depth;
     I.render_mode = p->render_mode;
     I.samples = 0;
-    I.reserved = 0;
+    I.reserved = (flags & RTW_ACCUM_CLAMP) ? rtw_f2u(level) : 0u;
+    a->level = (flags & RTW_ACCUM_CLAMP) ? level : 0.0f;
     I.seed = p->seed;
     I.world_fingerprint = g->fingerprint;
     I.slots = (int64_t)A.total;
@@ -6009,6 +6116,8 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     if (e == hipSuccess && (flags & RTW_ACCUM_MOMENTS)) e = hipMalloc(&a->squares, bytes);
     const size_t kept_bytes = std::max<size_t>(16, (size_t)A.total * sizeof(uint32_t));
     if (e == hipSuccess && (flags & RTW_ACCUM_FINITE)) e = hipMalloc(&a->kept, kept_bytes);
+    if (e == hipSuccess && (flags & RTW_ACCUM_CLAMP)) e = hipMalloc(&a->clamped, kept_bytes);
+    if (e == hipSuccess && (flags & RTW_ACCUM_CLAMP)) e = hipMalloc(&a->lost, bytes);
     a->tiles = a->active = A.total / (uint32_t)(A.tile_w * A.tile_h);
     const size_t stop_bytes = ((size_t)a->tiles + 1) * sizeof(uint32_t);
     if (flags & RTW_ACCUM_ADAPTIVE) {
@@ -6024,6 +6133,8 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     e = hipMemset(a->sums, 0, bytes);
     if (e == hipSuccess && a->squares) e = hipMemset(a->squares, 0, bytes);
     if (e == hipSuccess && a->kept) e = hipMemset(a->kept, 0, kept_bytes);
+    if (e == hipSuccess && a->clamped) e = hipMemset(a->clamped, 0, kept_bytes);
+    if (e == hipSuccess && a->lost) e = hipMemset(a->lost, 0, bytes);
     if (e == hipSuccess && a->tile_stop) e = hipMemset(a->tile_stop, 0, stop_bytes);
     if (e == hipSuccess && a->active_perm) e = hipMemset(a->active_perm, 0, stop_bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -6034,6 +6145,20 @@ extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_param
     g->accums.push_back(a);
     *out = a;
     return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t flags, rtw_accum** out) {
+    if (flags == (flags & (RTW_ACCUM_MOMENTS | RTW_ACCUM_ADAPTIVE | RTW_ACCUM_FINITE | RTW_ACCUM_CLAMP)) && (flags & RTW_ACCUM_CLAMP))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "RTW_ACCUM_CLAMP through rtw_accum_create: the clamp level is unknown; use rtw_accum_create_clamp");
+    return accum_create(g, p, flags, 0.0f, out);
+}
+
+extern "C" RTW_API int rtw_accum_create_clamp(rtw_gpu_world* g, const rtw_render_params* p, uint32_t flags, float level,
+                                              rtw_accum** out) {
+    if (!(flags & RTW_ACCUM_CLAMP)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_accum_create_clamp needs flags with RTW_ACCUM_CLAMP");
+    if (!rtw_clamp_level_ok(level))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "clamp: the level must be a finite f32 above 0 (not NaN, <= 0 or infinite)");
+    return accum_create(g, p, flags, level, out);
 }
 
 extern "C" RTW_API int rtw_accum_release(rtw_accum* a) {
@@ -6066,6 +6191,9 @@ extern "C" RTW_API int rtw_accum_add(rtw_accum* a, uint32_t n, void* stream) {
     HIP_TRY(hipSetDevice(a->g->device));
     AccumRun run{a->sums, a->squares, a->info.samples};
     run.kept = a->kept;
+    run.clamped = a->clamped;
+    run.lost = a->lost;
+    run.level = a->level;
     if (a->tile_stop && a->active < a->tiles) {  // (all active: exactly a plain moments accumulator's add)
         run.tile_stop = a->tile_stop;
         run.active_perm = a->active_perm;
@@ -6131,7 +6259,8 @@ extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* nois
 }
 
 namespace {
-int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop, uint32_t* host_kept = nullptr) {
+int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop, uint32_t* host_kept = nullptr,
+                 uint32_t* host_clamped = nullptr, float* host_lost = nullptr) {
     if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
@@ -6143,6 +6272,8 @@ int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* 
     if (a->squares) HIP_TRY(hipMemcpy(host_squares, a->squares, bytes, hipMemcpyDeviceToHost));
     if (host_stop) HIP_TRY(hipMemcpy(host_stop, a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (host_kept) HIP_TRY(hipMemcpy(host_kept, a->kept, (size_t)a->info.slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (host_clamped) HIP_TRY(hipMemcpy(host_clamped, a->clamped, (size_t)a->info.slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (host_lost) HIP_TRY(hipMemcpy(host_lost, a->lost, bytes, hipMemcpyDeviceToHost));
     return RTW_OK;
 }
 
@@ -6151,6 +6282,13 @@ int refuse_finite(const rtw_accum* a, const char* call) {
     if (!a || !(a->info.flags & RTW_ACCUM_FINITE)) return RTW_OK;
     return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(call) + ": the accumulator has RTW_ACCUM_FINITE, whose state includes "
                                                    "kept: use rtw_accum_export_state / rtw_accum_import_state");
+}
+
+// the three older pairs on an accumulator with RTW_ACCUM_CLAMP: its state includes clamped and lost
+int refuse_clamp(const rtw_accum* a, const char* call) {
+    if (!a || !(a->info.flags & RTW_ACCUM_CLAMP)) return RTW_OK;
+    return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(call) + ": the accumulator has RTW_ACCUM_CLAMP, whose state includes "
+                                                   "clamped and lost: use rtw_accum_export_state_clamp / rtw_accum_import_state_clamp");
 }
 
 // rtw_accum_export_state / rtw_accum_import_state: a pointer the flags call for is non-null, any other is null
@@ -6173,7 +6311,8 @@ int state_pointers(const rtw_accum* a, const void* squares, const void* stop, co
 }
 
 int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums, const float* host_squares,
-                 const uint32_t* host_stop, const uint32_t* host_kept = nullptr) {
+                 const uint32_t* host_stop, const uint32_t* host_kept = nullptr, const uint32_t* host_clamped = nullptr,
+                 const float* host_lost = nullptr) {
     if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     const rtw_accum_info& M = a->info;
@@ -6193,6 +6332,7 @@ int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sum
     if (info->seed != M.seed) return differs("seed");
     if (info->world_fingerprint != M.world_fingerprint) return differs("world_fingerprint");
     if (info->slots != M.slots) return differs("slots");
+    if ((M.flags & RTW_ACCUM_CLAMP) && info->reserved != M.reserved) return differs("clamp (the level, info.reserved)");
     if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
     if (a->tile_stop && !host_stop)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT,
@@ -6224,6 +6364,15 @@ int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sum
                     if (k != 0)
                         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "kept[" + std::to_string(slot) + "] = " + std::to_string(k) +
                                                                        ": a padding slot holds 0");
+                    if (host_clamped && host_clamped[slot] != 0)
+                        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "clamped[" + std::to_string(slot) + "] = " +
+                                                                       std::to_string(host_clamped[slot]) + ": a padding slot holds 0");
+                    for (int ch = 0; host_lost && ch < 3; ++ch)
+                        if (rtw_f2u(host_lost[3 * slot + ch]) != 0u)
+                            return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "lost[" + std::to_string(slot) + "] is not zero: a padding slot holds 0");
+                } else if (host_clamped && host_clamped[slot] > k) {
+                    return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "clamped[" + std::to_string(slot) + "] = " + std::to_string(host_clamped[slot]) +
+                                                                   " is above the slot's kept (" + std::to_string(k) + ")");
                 } else if (k > n) {
                     return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "kept[" + std::to_string(slot) + "] = " + std::to_string(k) +
                                                                    " is above the slot's sample count (" + std::to_string(n) + ")");
@@ -6239,6 +6388,8 @@ int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sum
         if (a->squares) HIP_TRY(hipMemcpy(a->squares, host_squares, bytes, hipMemcpyHostToDevice));
         if (host_stop) HIP_TRY(hipMemcpy(a->tile_stop, host_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
         if (host_kept) HIP_TRY(hipMemcpy(a->kept, host_kept, (size_t)M.slots * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (host_clamped) HIP_TRY(hipMemcpy(a->clamped, host_clamped, (size_t)M.slots * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (host_lost) HIP_TRY(hipMemcpy(a->lost, host_lost, bytes, hipMemcpyHostToDevice));
     }
     if (host_stop) a->h_stop.assign(host_stop, host_stop + a->tiles);
     a->active = active;
@@ -6257,19 +6408,19 @@ int64_t tile_pixels(const rtw_accum_info& I, uint32_t lt) {
 }  // namespace
 
 extern "C" RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares) {
-    if (refuse_finite(a, "rtw_accum_export") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
+    if (refuse_clamp(a, "rtw_accum_export") != RTW_OK || refuse_finite(a, "rtw_accum_export") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     return accum_export(a, host_sums, host_squares, nullptr);
 }
 
 extern "C" RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                         const float* host_squares) {
-    if (refuse_finite(a, "rtw_accum_import") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
+    if (refuse_clamp(a, "rtw_accum_import") != RTW_OK || refuse_finite(a, "rtw_accum_import") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     return accum_import(a, info, host_sums, host_squares, nullptr);
 }
 
 extern "C" RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop) {
     if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
-    if (refuse_finite(a, "rtw_accum_export_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
+    if (refuse_clamp(a, "rtw_accum_export_adaptive") != RTW_OK || refuse_finite(a, "rtw_accum_export_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     if (a->g && !a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
     return accum_export(a, host_sums, host_squares, host_stop);
 }
@@ -6277,7 +6428,7 @@ extern "C" RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums,
 extern "C" RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                                  const float* host_squares, const uint32_t* host_stop) {
     if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
-    if (refuse_finite(a, "rtw_accum_import_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
+    if (refuse_clamp(a, "rtw_accum_import_adaptive") != RTW_OK || refuse_finite(a, "rtw_accum_import_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     return accum_import(a, info, host_sums, host_squares, host_stop);
 }
 
@@ -6285,6 +6436,7 @@ extern "C" RTW_API int rtw_accum_export_state(rtw_accum* a, float* host_sums, fl
                                               uint32_t* host_kept) {
     if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (refuse_clamp(a, "rtw_accum_export_state") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     const int rc = state_pointers(a, host_squares, host_stop, host_kept);
     return rc != RTW_OK ? rc : accum_export(a, host_sums, host_squares, host_stop, host_kept);
 }
@@ -6294,12 +6446,52 @@ extern "C" RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info
                                               const uint32_t* host_kept) {
     if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    if (refuse_clamp(a, "rtw_accum_import_state") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
     const int rc = state_pointers(a, host_squares, host_stop, host_kept);
     return rc != RTW_OK ? rc : accum_import(a, info, host_sums, host_squares, host_stop, host_kept);
 }
 
+namespace {
+// the clamp pair's own two pointers, after state_pointers' rule for the other four
+int clamp_pointers(const rtw_accum* a, const void* squares, const void* stop, const void* kept, const void* clamped, const void* lost) {
+    if (!(a->info.flags & RTW_ACCUM_CLAMP))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator has no RTW_ACCUM_CLAMP: use rtw_accum_export_state / rtw_accum_import_state");
+    const int rc = state_pointers(a, squares, stop, kept);
+    if (rc != RTW_OK) return rc;
+    if (!clamped) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null clamped (the accumulator has RTW_ACCUM_CLAMP)");
+    if (!lost) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null lost (the accumulator has RTW_ACCUM_CLAMP)");
+    return RTW_OK;
+}
+}  // namespace
+
+extern "C" RTW_API int rtw_accum_export_state_clamp(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop,
+                                                    uint32_t* host_kept, uint32_t* host_clamped, float* host_lost) {
+    if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    const int rc = clamp_pointers(a, host_squares, host_stop, host_kept, host_clamped, host_lost);
+    return rc != RTW_OK ? rc : accum_export(a, host_sums, host_squares, host_stop, host_kept, host_clamped, host_lost);
+}
+
+extern "C" RTW_API int rtw_accum_import_state_clamp(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
+                                                    const float* host_squares, const uint32_t* host_stop,
+                                                    const uint32_t* host_kept, const uint32_t* host_clamped,
+                                                    const float* host_lost) {
+    if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
+    const int rc = clamp_pointers(a, host_squares, host_stop, host_kept, host_clamped, host_lost);
+    return rc != RTW_OK ? rc : accum_import(a, info, host_sums, host_squares, host_stop, host_kept, host_clamped, host_lost);
+}
+
 extern "C" RTW_API int rtw_accum_resolve_kept(rtw_accum* a, uint32_t* d_out, void* stream) {
     return accum_resolve(a, (float*)d_out, (hipStream_t)stream, 3);
+}
+
+extern "C" RTW_API int rtw_accum_resolve_clamped(rtw_accum* a, uint32_t* d_out, void* stream) {
+    return accum_resolve(a, (float*)d_out, (hipStream_t)stream, 4);
+}
+
+extern "C" RTW_API int rtw_accum_resolve_clamp_loss(rtw_accum* a, float* d_out, void* stream) {
+    return accum_resolve(a, d_out, (hipStream_t)stream, 5);
 }
 
 extern "C" RTW_API int rtw_accum_tile_stops(rtw_accum* a, uint32_t* host_stop) {
@@ -6366,7 +6558,7 @@ struct accum_sections {
     void* p[RTW_PARTS_MAX_SECTIONS];
     explicit accum_sections(const rtw_accum* a) {
         int n = 0;
-        for (void* q : {(void*)a->sums, (void*)a->squares, (void*)a->kept, (void*)a->tile_stop})
+        for (void* q : {(void*)a->sums, (void*)a->squares, (void*)a->kept, (void*)a->clamped, (void*)a->lost, (void*)a->tile_stop})
             if (q) p[n++] = q;
     }
 };
@@ -6381,6 +6573,7 @@ extern "C" RTW_API int rtw_accum_pack(rtw_accum* a, void* d_packed, void* stream
     if (rtw_parts_layout_of(&a->p, a->info.flags, a->info.part_count, &L) != 0 ||
         (uint32_t)rtw_parts_tiles(&L, a->info.part_index) != a->tiles)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
+    L.level = a->info.reserved;  // (0, or the level's bits with RTW_ACCUM_CLAMP)
     int rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
     HIP_TRY(rtw::parts_pack_launch(L, a->info.part_index, a->info.samples, accum_sections(a).p, d_packed, stream));
@@ -6400,6 +6593,7 @@ extern "C" RTW_API int rtw_accum_merge_parts(rtw_accum* whole, const void* d_gat
     rtw_parts_layout L;
     if (rtw_parts_layout_of(&a->p, flags, part_count, &L) != 0) return rtw::parts_refuse(0u, "params", at);
     if ((uint32_t)L.n_tiles != a->tiles) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "bad accumulator geometry");
+    L.level = a->info.reserved;  // (0, or the level's bits with RTW_ACCUM_CLAMP: a record of another level is refused)
     if (stride_bytes < (int64_t)(L.words * 4) || stride_bytes % 4 != 0 || ((uintptr_t)d_gathered & 3u) != 0)
         return rtw::parts_refuse(L.tag, "stride_bytes", at);
     // The headers (and, adaptive, the stop sections) come back first, after the work already on `stream` (the
@@ -6449,6 +6643,14 @@ extern "C" RTW_API int rtw_finite_accumulate_host(const float* colors, uint32_t 
                                                   float* squares, uint32_t* kept) {
     if (!colors || !sums || !kept) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     rtw_finite_accumulate(colors, n_samples, total, sums, squares, kept);
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_clamp_accumulate_host(const float* colors, uint32_t n_samples, uint32_t total, float level,
+                                                 float* sums, float* squares, uint32_t* kept, uint32_t* clamped, float* lost) {
+    if (!colors || !sums || !kept || !clamped || !lost) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!rtw_clamp_level_ok(level)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "clamp: the level must be a finite f32 above 0");
+    rtw_clamp_accumulate(colors, n_samples, total, level, sums, squares, kept, clamped, lost);
     return RTW_OK;
 }
 

@@ -19,6 +19,7 @@
 
 #include "rtw_common.h"
 #include "../../include/rtw_aov_parts.h"
+#include "../../include/rtw_clamp.h"
 
 #define RTW_PARTS_BLOCK 256
 
@@ -141,7 +142,7 @@ hipError_t parts_pack_launch(const rtw_parts_layout& L, int32_t r, uint32_t samp
     // (at least one block: the header's)
     const uint32_t blocks = std::max(1u, parts_args(L, own_tiles, arrays, aligned16(d_packed), true, &A));
     const uint32_t header[RTW_PARTS_HEADER_WORDS] = {RTW_PARTS_VERSION, L.kind, (uint32_t)r, (uint32_t)L.part_count,
-                                                     samples, own_tiles * (uint32_t)L.per_tile, own_tiles, L.tag};
+                                                     samples, own_tiles * (uint32_t)L.per_tile, own_tiles, rtw_parts_last_word(&L)};
     for (int h = 0; h < RTW_PARTS_HEADER_WORDS; ++h) A.header[h] = header[h];
     hipLaunchKernelGGL(parts_pack_kernel, dim3(blocks), dim3(RTW_PARTS_BLOCK), 0, stream, A, (uint32_t*)d_packed);
     return hipGetLastError();
@@ -178,7 +179,8 @@ int packed_bytes(int built, const rtw_parts_layout& L, const char* refusal, int6
 
 // the two host twins: `built` is the layout builder's result, `want` the entry point's arrays, `when` the end of the
 // message about an array that does not go with the kind word
-int merge_host(int built, const rtw_parts_layout& L, uint32_t tag, uint32_t kind, const char* when, const HostArray (&want)[4],
+template <size_t K>
+int merge_host(int built, const rtw_parts_layout& L, uint32_t tag, uint32_t kind, const char* when, const HostArray (&want)[K],
                const void* gathered, int64_t stride_bytes, uint32_t* samples) {
     const int32_t none[2] = {0, 0};
     for (const auto& w : want)
@@ -188,7 +190,7 @@ int merge_host(int built, const rtw_parts_layout& L, uint32_t tag, uint32_t kind
     if (built != 0) return rtw::parts_refuse(tag, "params", none);
     uint32_t* dst[RTW_PARTS_MAX_SECTIONS];
     int n = 0;
-    for (int rank = 0; rank < 4; ++rank)
+    for (int rank = 0; rank < (int)K; ++rank)
         for (const auto& w : want)
             for (int k = 0; w.rank == rank && w.p && k < w.planes; ++k)
                 dst[n++] = (uint32_t*)w.p + (size_t)k * (size_t)L.n_tiles * (size_t)L.per_tile;
@@ -230,9 +232,31 @@ extern "C" RTW_API int rtw_accum_merge_parts_host(const rtw_render_params* param
                                                   int64_t stride_bytes, int32_t part_count, float* sums, float* squares,
                                                   uint32_t* kept, uint32_t* tile_stop, uint32_t* samples) {
     if (!params || !gathered || !sums || !samples) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (flags & RTW_ACCUM_CLAMP)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_accum_merge_parts_host: the flags hold RTW_ACCUM_CLAMP, whose records carry a level, "
+                                                   "clamped and lost: use rtw_accum_merge_parts_host_clamp");
     const HostArray want[4] = {{0u, sums, "sums", 0, 1}, {RTW_ACCUM_MOMENTS, squares, "squares", 1, 1},
                                {RTW_ACCUM_ADAPTIVE, tile_stop, "tile_stop", 3, 1}, {RTW_ACCUM_FINITE, kept, "kept", 2, 1}};
     rtw_parts_layout L;
     return merge_host(rtw_parts_layout_of(params, flags, part_count, &L), L, 0u, flags, "flags call for it", want, gathered, stride_bytes,
                       samples);
+}
+
+extern "C" RTW_API int rtw_accum_merge_parts_host_clamp(const rtw_render_params* params, uint32_t flags, float level,
+                                                        const void* gathered, int64_t stride_bytes, int32_t part_count,
+                                                        float* sums, float* squares, uint32_t* kept, uint32_t* clamped,
+                                                        float* lost, uint32_t* tile_stop, uint32_t* samples) {
+    if (!params || !gathered || !sums || !samples) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+    if (!(flags & RTW_ACCUM_CLAMP)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_accum_merge_parts_host_clamp needs flags with RTW_ACCUM_CLAMP");
+    if (!rtw_clamp_level_ok(level)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "clamp: the level must be a finite f32 above 0");
+    const HostArray want[6] = {{0u, sums, "sums", 0, 1},
+                               {RTW_ACCUM_MOMENTS, squares, "squares", 1, 1},
+                               {RTW_ACCUM_ADAPTIVE, tile_stop, "tile_stop", 5, 1},
+                               {RTW_ACCUM_FINITE, kept, "kept", 2, 1},
+                               {RTW_ACCUM_CLAMP, clamped, "clamped", 3, 1},
+                               {RTW_ACCUM_CLAMP, lost, "lost", 4, 1}};
+    rtw_parts_layout L;
+    const int built = rtw_parts_layout_of(params, flags, part_count, &L);
+    if (built == 0) rtw_parts_set_level(&L, level);
+    return merge_host(built, L, 0u, flags, "flags call for it", want, gathered, stride_bytes, samples);
 }

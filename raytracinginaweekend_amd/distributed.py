@@ -240,7 +240,7 @@ class DistributedAccumulator(_DistributedRecords):
     local decision plus one all_reduce of the two counts (the decisions are per tile, so they are one GPU's);
     `sync` packs every rank's state, gathers the records onto rank 0 with one collective and merges them into
     `whole`, which then is, bit for bit, the accumulator one GPU would hold after the same calls: read it through
-    its own API (`image`, `stderr`, `noise`, `sample_counts`, `kept_counts`, `tile_stops`, `denoised`, `state`).
+    its own API (`image`, `stderr`, `noise`, `sample_counts`, `kept_counts`, `clamped_counts`, `clamp_loss`, `tile_stops`, `denoised`, `state`).
     With the nccl backend the device tensors are gathered; with any other (gloo) the record is staged through a
     host tensor on both sides, which also lets several ranks share one GPU.  world_size 1 is a pass-through
     without a collective: `local` is `whole`.
@@ -249,10 +249,11 @@ class DistributedAccumulator(_DistributedRecords):
 
     def __init__(self, world: World | DeviceWorld, size: Size2i, max_depth: int, rank: int = 0, world_size: int = 1,
                  device: int = 0, *, seed: int = DEFAULT_SEED, tile: tuple[int, int] = (8, 8), moments: bool = False,
-                 adaptive: bool = False, finite: bool = False, render_mode: RenderMode = RenderMode.Default):
+                 adaptive: bool = False, finite: bool = False, render_mode: RenderMode = RenderMode.Default,
+                 clamp: float | None = None):
         from .progressive import Accumulator
 
-        kw = dict(seed=seed, device=device, tile=tile, moments=moments, adaptive=adaptive, finite=finite)
+        kw = dict(seed=seed, device=device, tile=tile, moments=moments, adaptive=adaptive, finite=finite, clamp=clamp)
 
         def make(dworld, part):
             if part is None:

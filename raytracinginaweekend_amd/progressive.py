@@ -21,6 +21,14 @@ pixel's own kept count.  On a pixel with no rejected sample every value is the p
 Dropping samples biases the estimate (the dropped paths carried energy): a plain accumulator's `image()` and
 `render` stay the exact reference image.  Combines with moments and adaptive.  `render_finite` is the one-call form.
 
+With ``clamp=L`` (implies finite; include/rtw_clamp.h) the accumulate pass also scales every finite sample whose largest
+channel exceeds L down to it (firefly control: one sample of 27 no longer holds a tile's noise estimate up).  The hue
+is kept and no accumulated channel exceeds L.  `clamped_counts()` holds the samples it scaled per pixel and
+`clamp_loss()` the mean radiance it removed, so `image() + clamp_loss()` is the unclamped finite mean up to rounding.
+`image()`, `stderr()`, `noise()`, `adapt()` and `denoised()` work on the clamped sums.  On a pixel without a clamped
+sample every value is the finite accumulator's, bit for bit.  Clamping biases the estimate: it is opt-in.
+`render_clamped` is the one-call form.
+
 The reference's thread_count > 1 splits a frame's samples into planes by the *final* spp
 (split_work_tasks, rendering.rs:222-237), so a prefix of such a frame is not a frame: accumulators
 render thread_count 1 only.
@@ -60,12 +68,13 @@ RECORD_HEADER_WORDS = _parts.HEADER_WORDS
 
 def record_layout(width: int, height: int, tile: tuple[int, int], flags: int, part_count: int) -> dict:
     """The packed record of include/rtw_parts.h in numpy's terms: per_tile, n_tiles, tiles0, slots0, the word
-    offsets sums / squares / kept / stop (None: the flags do not call for the section) and words."""
+    offsets sums / squares / kept / clamped / lost / stop (None: the flags do not call for the section) and words."""
     tw, th = tile
     per_tile = tw * th
     lay = _parts.section_offsets(-(-width // tw) * -(-height // th), part_count, per_tile,
                                  (("sums", True, 3 * per_tile), ("squares", flags & N.ACCUM_MOMENTS, 3 * per_tile),
-                                  ("kept", flags & N.ACCUM_FINITE, per_tile), ("stop", flags & N.ACCUM_ADAPTIVE, 1)))
+                                  ("kept", flags & N.ACCUM_FINITE, per_tile), ("clamped", flags & N.ACCUM_CLAMP, per_tile),
+                                  ("lost", flags & N.ACCUM_CLAMP, 3 * per_tile), ("stop", flags & N.ACCUM_ADAPTIVE, 1)))
     lay["per_tile"] = per_tile
     return lay
 
@@ -76,7 +85,9 @@ class AccumState:
     moments, the sums of squares (float32, shape (slots, 3); padding slots of edge tiles hold zeros);
     of an adaptive accumulator also the stop map (uint32, shape (tiles,), tiles = slots / (tile_width *
     tile_height): 0 = active, else the sample count the tile stopped at); of a finite accumulator also the kept
-    counts (uint32, shape (slots,): the samples that entered each slot's sums; padding slots hold 0)."""
+    counts (uint32, shape (slots,): the samples that entered each slot's sums; padding slots hold 0); of a clamp
+    accumulator also the clamped counts (uint32, shape (slots,)) and the lost sums (float32, shape (slots, 3)), zero
+    in padding slots, and the level: `clamp`, whose f32 bits the header's `reserved` holds."""
 
     version: int
     flags: int
@@ -97,6 +108,15 @@ class AccumState:
     squares: np.ndarray | None = None
     tile_stop: np.ndarray | None = None
     kept: np.ndarray | None = None
+    clamped: np.ndarray | None = None
+    lost: np.ndarray | None = None
+
+    @property
+    def clamp(self) -> float | None:
+        """The clamp level (None: the flags hold no RTW_ACCUM_CLAMP)."""
+        if not int(self.flags) & N.ACCUM_CLAMP:
+            return None
+        return float(np.array(int(self.reserved), np.uint32).view(np.float32))
 
     def header(self) -> dict:
         return {n: int(getattr(self, n)) for n in _HEADER}
@@ -108,7 +128,8 @@ class AccumState:
 
     def save(self, path) -> None:
         """One .npz of plain arrays (numpy.savez): a 0-d array per header field, `sums`, `squares`
-        when the accumulator kept moments, `tile_stop` when it was adaptive and `kept` when it was finite."""
+        when the accumulator kept moments, `tile_stop` when it was adaptive, `kept` when it was finite and `clamped`
+        and `lost` when it clamped (the level travels in `reserved`)."""
         arrays = {n: np.asarray(getattr(self, n), dtype=t) for n, t in _HEADER.items()}
         arrays["sums"] = np.ascontiguousarray(self.sums, np.float32)
         if self.squares is not None:
@@ -123,6 +144,16 @@ class AccumState:
             if kept.dtype != np.uint32 or kept.shape != (int(self.slots),):
                 raise ValueError("kept is not uint32 of shape (slots,)")
             arrays["kept"] = np.ascontiguousarray(kept)
+        if (self.clamped is None) != (self.lost is None):
+            raise ValueError("clamped and lost go together")
+        if self.clamped is not None:
+            clamped, lost = np.asarray(self.clamped), np.asarray(self.lost)
+            if clamped.dtype != np.uint32 or clamped.shape != (int(self.slots),):
+                raise ValueError("clamped is not uint32 of shape (slots,)")
+            if lost.dtype != np.float32 or lost.shape != (int(self.slots), 3):
+                raise ValueError("lost is not float32 of shape (slots, 3)")
+            arrays["clamped"] = np.ascontiguousarray(clamped)
+            arrays["lost"] = np.ascontiguousarray(lost)
         with open(path, "wb") as f:
             np.savez(f, **arrays)
 
@@ -132,7 +163,7 @@ class AccumState:
         arrays `save` writes is refused."""
         with np.load(path, allow_pickle=False) as z:
             names = set(z.files)
-            known = set(_HEADER) | {"sums", "squares", "tile_stop", "kept"}
+            known = set(_HEADER) | {"sums", "squares", "tile_stop", "kept", "clamped", "lost"}
             if names - known:
                 raise ValueError(f"not an accumulator checkpoint: unexpected entries {sorted(names - known)}")
             missing = (set(_HEADER) | {"sums"}) - names
@@ -145,7 +176,7 @@ class AccumState:
                     raise ValueError(f"accumulator checkpoint: bad header field {n}")
                 vals[n] = int(a)
             arrays = {}
-            for n in ("sums", "squares"):
+            for n in ("sums", "squares", "lost"):
                 if n not in names:
                     continue
                 a = z[n]
@@ -162,8 +193,15 @@ class AccumState:
                 if a.dtype != np.uint32 or a.shape != (vals["slots"],):
                     raise ValueError("accumulator checkpoint: kept is not uint32 of shape (slots,)")
                 arrays["kept"] = a
+            if "clamped" in names:
+                a = z["clamped"]
+                if a.dtype != np.uint32 or a.shape != (vals["slots"],):
+                    raise ValueError("accumulator checkpoint: clamped is not uint32 of shape (slots,)")
+                arrays["clamped"] = a
+            if ("clamped" in names) != ("lost" in names):
+                raise ValueError("accumulator checkpoint: clamped and lost go together")
         return cls(**vals, sums=arrays["sums"], squares=arrays.get("squares"), tile_stop=arrays.get("tile_stop"),
-                   kept=arrays.get("kept"))
+                   kept=arrays.get("kept"), clamped=arrays.get("clamped"), lost=arrays.get("lost"))
 
     def _frame_tiles(self) -> int:
         return -(-int(self.width) // int(self.tile_width)) * -(-int(self.height) // int(self.tile_height))
@@ -173,10 +211,13 @@ class AccumState:
         """The whole image's state (part (0, 1)) from the states of parts (0..N-1, N) of one frame, in any order:
         a placement of tile blocks, bit for bit the state one accumulator would hold.  Raises ValueError naming
         the field when the states differ in geometry, max_depth, render_mode, seed, world_fingerprint, version or
-        flags, when a part is missing or comes twice, when slots or an array does not fit the part, and when
-        samples differ between parts that are not adaptive.  Adaptive: samples is the largest of the parts' (a
+        flags, when a part is missing or comes twice, when slots or an array does not fit the part, when the clamp
+        levels differ ("clamp"), and when samples differ between parts that are not adaptive.  Adaptive: samples is the largest of the parts' (a
         part whose tiles have all stopped no longer counts, `Accumulator.add`)."""
         states = list(states)
+        for s in states[1:]:  # (before `reserved`, which holds the level's bits)
+            if int(s.flags) == int(states[0].flags) and int(s.flags) & N.ACCUM_CLAMP and int(s.reserved) != int(states[0].reserved):
+                raise ValueError(f"the states are not parts of one frame: clamp differs ({s.clamp!r} against {states[0].clamp!r})")
         by_part = _parts.parts_in_order(states, ("version", "flags", "width", "height", "tile_width", "tile_height", "part_count",
                                                  "max_depth", "render_mode", "reserved", "seed", "world_fingerprint"))
         first, count = states[0], len(by_part)
@@ -187,6 +228,8 @@ class AccumState:
         sums = np.zeros((slots, 3), np.float32)
         squares = np.zeros((slots, 3), np.float32) if flags & N.ACCUM_MOMENTS else None
         kept = np.zeros(slots, np.uint32) if flags & N.ACCUM_FINITE else None
+        clamped = np.zeros(slots, np.uint32) if flags & N.ACCUM_CLAMP else None
+        lost = np.zeros((slots, 3), np.float32) if flags & N.ACCUM_CLAMP else None
         stop = np.zeros(n_tiles, np.uint32) if adaptive else None
         samples = int(first.samples)
         for r in range(count):
@@ -198,6 +241,7 @@ class AccumState:
                 raise ValueError(f"part {r}: samples differs (only adaptive parts may differ)")
             samples = max(samples, int(s.samples))
             for name, dst, shape in (("sums", sums, (at.size, 3)), ("squares", squares, (at.size, 3)), ("kept", kept, (at.size,)),
+                                     ("clamped", clamped, (at.size,)), ("lost", lost, (at.size, 3)),
                                      ("tile_stop", stop, (tiles.size,))):
                 src = getattr(s, name)
                 if (src is None) != (dst is None):
@@ -215,7 +259,7 @@ class AccumState:
                     raise ValueError(f"part {r}: tile_stop[{int(np.flatnonzero(bad)[0])}] is 1 or above the part's samples")
         head = first.header()
         head.update(part_index=0, part_count=1, samples=samples, slots=slots)
-        return cls(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept)
+        return cls(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept, clamped=clamped, lost=lost)
 
     def split(self, part_count: int) -> list["AccumState"]:
         """The inverse of `merge`: the states of parts (0..part_count-1, part_count) of this whole-image state.  A
@@ -244,7 +288,9 @@ class AccumState:
             head.update(part_index=r, part_count=part_count, samples=samples, slots=int(at.size))
             out.append(AccumState(**head, sums=np.ascontiguousarray(self.sums[at]),
                                   squares=None if self.squares is None else np.ascontiguousarray(self.squares[at]),
-                                  tile_stop=stop, kept=None if self.kept is None else np.ascontiguousarray(self.kept[at])))
+                                  tile_stop=stop, kept=None if self.kept is None else np.ascontiguousarray(self.kept[at]),
+                                  clamped=None if self.clamped is None else np.ascontiguousarray(self.clamped[at]),
+                                  lost=None if self.lost is None else np.ascontiguousarray(self.lost[at])))
         return out
 
     def packed(self, stride_bytes: int | None = None) -> np.ndarray:
@@ -252,11 +298,13 @@ class AccumState:
         with zeros to `stride_bytes`: what a rank without device-aware collectives sends."""
         count = max(1, int(self.part_count))
         lay = record_layout(int(self.width), int(self.height), (int(self.tile_width), int(self.tile_height)), int(self.flags), count)
-        sections = (("sums", self.sums), ("squares", self.squares), ("kept", self.kept), ("stop", self.tile_stop))
+        sections = (("sums", self.sums), ("squares", self.squares), ("kept", self.kept), ("clamped", self.clamped),
+                    ("lost", self.lost), ("stop", self.tile_stop))
         for name, arr in sections:
             if (arr is None) != (lay[name] is None):
                 raise ValueError(f"{name} does not go with the flags")
-        header = (RECORD_VERSION, int(self.flags), int(self.part_index), count, int(self.samples), int(self.slots), self.tiles, 0)
+        header = (RECORD_VERSION, int(self.flags), int(self.part_index), count, int(self.samples), int(self.slots), self.tiles,
+                  int(self.reserved) if int(self.flags) & N.ACCUM_CLAMP else 0)
         return _parts.pack_record(header, lay["words"], stride_bytes, [(lay[name], arr) for name, arr in sections if arr is not None])
 
 
@@ -280,7 +328,8 @@ class Accumulator:
     def __init__(self, world: World | DeviceWorld, size: Size2i, max_depth: int,
                  render_mode: RenderMode = RenderMode.Default, *, seed: int = DEFAULT_SEED, device: int = 0,
                  tile: tuple[int, int] = (8, 8), part: tuple[int, int] = (0, 1), layout: int = N.LAYOUT_IMAGE,
-                 moments: bool = False, adaptive: bool = False, finite: bool = False, thread_count: int = 1):
+                 moments: bool = False, adaptive: bool = False, finite: bool = False, thread_count: int = 1,
+                 clamp: float | None = None):
         self._h = None
         self._denoiser = None  # made by the first denoised()
         self.dworld = world if isinstance(world, DeviceWorld) else DeviceWorld(world, device)
@@ -288,13 +337,17 @@ class Accumulator:
         self.size = size
         self.adaptive = bool(adaptive)
         self.moments = bool(moments) or self.adaptive
-        self.finite = bool(finite)
+        self.clamp = None if clamp is None else float(np.float32(clamp))  # the level (an f32), or None
+        self.finite = bool(finite) or self.clamp is not None
         self.params = render_params(size, 0, max_depth, render_mode, seed, tile=tile, part=part, layout=layout,
                                     thread_count=thread_count)
         h = C.c_void_p()
         flags = (N.ACCUM_MOMENTS if self.moments else 0) | (N.ACCUM_ADAPTIVE if self.adaptive else 0)
         flags |= N.ACCUM_FINITE if self.finite else 0
-        check(lib().rtw_accum_create(self.dworld._h, C.byref(self.params), flags, C.byref(h)))
+        if self.clamp is not None:
+            check(lib().rtw_accum_create_clamp(self.dworld._h, C.byref(self.params), flags | N.ACCUM_CLAMP, self.clamp, C.byref(h)))
+        else:
+            check(lib().rtw_accum_create(self.dworld._h, C.byref(self.params), flags, C.byref(h)))
         self._h = h
         self._out = None
 
@@ -447,6 +500,17 @@ class Accumulator:
 
         return self._resolved(lib().rtw_accum_resolve_kept, 1, torch.int32).view(np.uint32)
 
+    def clamped_counts(self) -> np.ndarray:
+        """The samples of each pixel the clamp scaled down (clamp=L), uint32, laid out as `kept_counts()`."""
+        import torch
+
+        return self._resolved(lib().rtw_accum_resolve_clamped, 1, torch.int32).view(np.uint32)
+
+    def clamp_loss(self) -> np.ndarray:
+        """The mean radiance the clamp removed from each pixel, lost / kept per channel (clamp=L), laid out as
+        `image()`: (W*H, 3) f32."""
+        return self._resolved(lib().rtw_accum_resolve_clamp_loss)
+
     def rejected_counts(self) -> np.ndarray:
         """The samples of each pixel that were left out: `sample_counts()` - `kept_counts()` (finite=True)."""
         return self.sample_counts() - self.kept_counts()
@@ -474,8 +538,14 @@ class Accumulator:
         i = self.info()
         sums = np.zeros((i.slots, 3), np.float32)
         squares = np.zeros((i.slots, 3), np.float32) if self.moments else None
-        stop = kept = None
-        if self.finite:  # the one pair for every flag combination
+        stop = kept = clamped = lost = None
+        if self.clamp is not None:
+            stop = np.zeros(self.tiles, np.uint32) if self.adaptive else None
+            kept, clamped, lost = np.zeros(i.slots, np.uint32), np.zeros(i.slots, np.uint32), np.zeros((i.slots, 3), np.float32)
+            check(lib().rtw_accum_export_state_clamp(self._h, _f32p(sums), _f32p(squares) if squares is not None else None,
+                                                     _u32p(stop) if stop is not None else None, _u32p(kept), _u32p(clamped),
+                                                     _f32p(lost)))
+        elif self.finite:  # the one pair for every flag combination
             stop = np.zeros(self.tiles, np.uint32) if self.adaptive else None
             kept = np.zeros(i.slots, np.uint32)
             check(lib().rtw_accum_export_state(self._h, _f32p(sums), _f32p(squares) if squares is not None else None,
@@ -486,7 +556,7 @@ class Accumulator:
         else:
             check(lib().rtw_accum_export(self._h, _f32p(sums), _f32p(squares) if squares is not None else None))
         return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, sums=sums, squares=squares, tile_stop=stop,
-                          kept=kept)
+                          kept=kept, clamped=clamped, lost=lost)
 
     def packed_bytes(self) -> int:
         """The bytes of this accumulator's packed record (the same for every part of its part_count)."""
@@ -502,8 +572,8 @@ class Accumulator:
     def merge_parts(self, gathered, stride_bytes: int, part_count: int, stream_ptr: int | None = None) -> None:
         """Replaces this whole-image accumulator's state (part (0, 1)) by the merge of `part_count` packed records,
         record r at byte r * stride_bytes of the device tensor `gathered` (rtw_accum_merge_parts).  Raises
-        RtwError naming the field for records of another version, flags, order, part_count or geometry, a bad
-        stride, and unequal samples where not adaptive; nothing is launched then."""
+        RtwError naming the field for records of another version, flags, order, part_count, geometry or clamp
+        level, a bad stride, and unequal samples where not adaptive; nothing is launched then."""
         need = max(0, part_count - 1) * stride_bytes + N.packed_bytes(self.params, int(self.info().flags), max(1, part_count))
         if not gathered.is_cuda or not gathered.is_contiguous():
             raise ValueError("merge_parts needs a contiguous device tensor")
@@ -523,7 +593,19 @@ class Accumulator:
         if sums.size != 3 * state.slots or (squares is not None and squares.size != sums.size):
             raise ValueError("state arrays do not hold 3 * slots floats")
         sq = _f32p(squares) if squares is not None else None
-        if self.finite or state.kept is not None:  # the one pair: it refuses what the flags do not call for
+        if self.clamp is not None or state.clamped is not None or state.lost is not None:
+            # the clamp pair: it refuses what the flags do not call for, and another level by name
+            arr = {}
+            for n, t, shape in (("tile_stop", np.uint32, (self.tiles,)), ("kept", np.uint32, (state.slots,)),
+                                ("clamped", np.uint32, (state.slots,)), ("lost", np.float32, (state.slots, 3))):
+                v = getattr(state, n)
+                arr[n] = None if v is None else np.ascontiguousarray(v, t)
+                if arr[n] is not None and arr[n].shape != shape:
+                    raise ValueError(f"state.{n} does not have shape {shape}")
+            ptr = {n: None if v is None else (_f32p(v) if n == "lost" else _u32p(v)) for n, v in arr.items()}
+            check(lib().rtw_accum_import_state_clamp(self._h, C.byref(i), _f32p(sums), sq, ptr["tile_stop"], ptr["kept"],
+                                                     ptr["clamped"], ptr["lost"]))
+        elif self.finite or state.kept is not None:  # the one pair: it refuses what the flags do not call for
             stop = None if state.tile_stop is None else np.ascontiguousarray(state.tile_stop, np.uint32)
             kept = None if state.kept is None else np.ascontiguousarray(state.kept, np.uint32)
             if stop is not None and stop.shape != (self.tiles,):
@@ -560,6 +642,15 @@ def merge_parts_host(like: AccumState, gathered: np.ndarray, stride_bytes: int, 
     kept = np.zeros(slots, np.uint32) if flags & N.ACCUM_FINITE else None
     stop = np.zeros(n_tiles, np.uint32) if flags & N.ACCUM_ADAPTIVE else None
     samples = C.c_uint32()
+    if flags & N.ACCUM_CLAMP:  # (records of another level than `like`'s are refused naming clamp)
+        clamped, lost = np.zeros(slots, np.uint32), np.zeros((slots, 3), np.float32)
+        check(lib().rtw_accum_merge_parts_host_clamp(C.byref(p), flags, like.clamp, C.c_void_p(buf.ctypes.data), stride_bytes,
+                                                     part_count, _f32p(sums), _f32p(squares) if squares is not None else None,
+                                                     _u32p(kept) if kept is not None else None, _u32p(clamped), _f32p(lost),
+                                                     _u32p(stop) if stop is not None else None, C.byref(samples)))
+        head = like.header()
+        head.update(part_index=0, part_count=1, samples=int(samples.value), slots=slots)
+        return AccumState(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept, clamped=clamped, lost=lost)
     check(lib().rtw_accum_merge_parts_host(C.byref(p), flags, C.c_void_p(buf.ctypes.data), stride_bytes, part_count,
                                            _f32p(sums), _f32p(squares) if squares is not None else None,
                                            _u32p(kept) if kept is not None else None,
@@ -601,10 +692,25 @@ def render_finite(size: Size2i, spp: int, max_depth: int, world, **kw):
         acc.release()
 
 
+def render_clamped(size: Size2i, spp: int, max_depth: int, world, clamp: float, **kw):
+    """`spp` samples per pixel through a clamp accumulator of level `clamp`: returns (image, clamped, loss), the mean
+    of each pixel's clamped finite samples ((W*H, 3) f32), the samples the clamp scaled per pixel ((W*H, 1) uint32)
+    and the mean radiance it removed ((W*H, 3) f32)."""
+    if spp < 1:
+        raise ValueError("spp must be >= 1")
+    kw["clamp"] = clamp
+    acc = Accumulator(world, size, max_depth, **kw)
+    try:
+        acc.add(spp)
+        return acc.image(), acc.clamped_counts(), acc.clamp_loss()
+    finally:
+        acc.release()
+
+
 def render_to_noise(size: Size2i, max_depth: int, world, target: float, max_samples: int, batch: int = 16, **kw):
     """Adds `batch` samples at a time (the last batch cut to `max_samples`) until noise() <= target or
-    samples == max_samples.  Returns (image, samples, noise).  Keyword arguments go to `Accumulator` (finite=True
-    among them)."""
+    samples == max_samples.  Returns (image, samples, noise).  Keyword arguments go to `Accumulator` (finite=True and
+    clamp=L among them)."""
     if max_samples < 2 or batch < 1:
         raise ValueError("max_samples must be >= 2 and batch >= 1")
     kw["moments"] = True
