@@ -3343,101 +3343,49 @@ __device__ __forceinline__ bool slot_pixel(const SlotGeom& G, uint32_t slot, int
     py = (tile / G.tiles_x) * G.tile_h + it / G.tile_w;
     return px < G.width && py < G.height;
 }
-// An accumulator's add with RTW_ACCUM_MOMENTS: accumulate_kernel's in-order sum onto the accumulator's
-// own running sum, and per channel sq = add(sq, mul(c, c)) (two roundings: no contraction in this build).
+// An accumulator's add: accumulate_kernel's in-order sum onto the accumulator's own running sum.  One body, the
+// kernels below are its instantiations.  One slot per lane; what the flags keep stays in registers over the launch's
+// samples, so each state array takes one read and one write per launch, and an array the flags do not call for is
+// not read (its pointer may be null).
+//   MOMENTS (RTW_ACCUM_MOMENTS): per channel sq = add(sq, mul(c, c)) (two roundings: no contraction in this build).
+//   FINITE (RTW_ACCUM_FINITE, rtw_finite.h): a sample with a NaN or infinite channel adds nothing and is not counted
+//   in kept.
+//   CLAMP (RTW_ACCUM_CLAMP, rtw_clamp.h; with FINITE): a finite sample whose largest channel exceeds `level` is
+//   scaled down to it first; what the scaling took goes to lost and the sample is counted in clamped.
 // tile_stop (adaptive accumulators with a stopped tile, else null): the slots of stopped tiles are skipped --
 // the launch rendered the active tiles only, so their colour-buffer entries are stale.
-__global__ void accumulate_moments_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G,
-                                          float* __restrict__ sums, float* __restrict__ squares,
-                                          const uint32_t* __restrict__ tile_stop) {
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t px, py;
-    if (!slot_pixel(G, slot, px, py)) return;
-    if (tile_stop && tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)] != 0) return;
-    float* S = sums + 3 * (size_t)slot;
-    float* Q = squares + 3 * (size_t)slot;
-    V3 sum = v3(S[0], S[1], S[2]), sq = v3(Q[0], Q[1], Q[2]);
-    const float* c = colors + 3 * (size_t)slot;
-    for (uint32_t s = 0; s < n_samples; ++s, c += 3 * (size_t)G.total) {
-        const V3 col = v3(c[0], c[1], c[2]);
-        sum = add(sum, col);
-        sq = add(sq, conv(col, col));
-    }
-    S[0] = sum.x;
-    S[1] = sum.y;
-    S[2] = sum.z;
-    Q[0] = sq.x;
-    Q[1] = sq.y;
-    Q[2] = sq.z;
-}
-// An accumulator's add with RTW_ACCUM_FINITE (rtw_finite.h): accumulate_moments_kernel's pass, but a sample with a
-// NaN or infinite channel adds nothing and is not counted.  One slot per lane; sum, sq and kept stay in registers
-// over the launch's samples, so each array takes one read and one write per launch.  MOMENTS false: no squares
-// (the pointer is not read).  Stopped tiles are skipped as above.
-template <bool MOMENTS>
-__global__ void accumulate_finite_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G,
-                                         float* __restrict__ sums, float* __restrict__ squares,
-                                         uint32_t* __restrict__ kept, const uint32_t* __restrict__ tile_stop) {
+template <bool MOMENTS, bool FINITE, bool CLAMP>
+__device__ __forceinline__ void accumulate_body(const float* __restrict__ colors, uint32_t n_samples, const SlotGeom& G,
+                                                float level, float* __restrict__ sums, float* __restrict__ squares,
+                                                uint32_t* __restrict__ kept, uint32_t* __restrict__ clamped,
+                                                float* __restrict__ lost, const uint32_t* __restrict__ tile_stop) {
+    static_assert(FINITE || !CLAMP, "the clamp sees finite samples only");
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     int32_t px, py;
     if (!slot_pixel(G, slot, px, py)) return;
     if (tile_stop && tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)] != 0) return;
     float* S = sums + 3 * (size_t)slot;
     float* Q = MOMENTS ? squares + 3 * (size_t)slot : nullptr;
-    V3 sum = v3(S[0], S[1], S[2]), sq = v3(0.0f, 0.0f, 0.0f);
+    float* D = CLAMP ? lost + 3 * (size_t)slot : nullptr;
+    V3 sum = v3(S[0], S[1], S[2]), sq = v3(0.0f, 0.0f, 0.0f), gone = v3(0.0f, 0.0f, 0.0f);
     if (MOMENTS) sq = v3(Q[0], Q[1], Q[2]);
-    uint32_t k = kept[slot];
-    const float* c = colors + 3 * (size_t)slot;
-    for (uint32_t s = 0; s < n_samples; ++s, c += 3 * (size_t)G.total) {
-        const V3 col = v3(c[0], c[1], c[2]);
-        // (a branch, not selects: the select form compiled to 52 B of scratch and ran the pass 4.5x slower,
-        // profiles/r12/pass_ab_select.txt)
-        if (!rtw_finite_sample(col.x, col.y, col.z)) continue;
-        sum = add(sum, col);
-        if (MOMENTS) sq = add(sq, conv(col, col));
-        ++k;
-    }
-    S[0] = sum.x;
-    S[1] = sum.y;
-    S[2] = sum.z;
-    if (MOMENTS) {
-        Q[0] = sq.x;
-        Q[1] = sq.y;
-        Q[2] = sq.z;
-    }
-    kept[slot] = k;
-}
-// An accumulator's add with RTW_ACCUM_CLAMP (rtw_clamp.h): accumulate_finite_kernel's pass, and a finite sample whose
-// largest channel exceeds `level` is scaled down to it first; what the scaling took goes to lost and the sample is
-// counted in clamped.  One slot per lane; sum, sq, lost, kept and clamped stay in registers over the launch's
-// samples, so each state array takes one read and one write per launch.  The rejection and the clamp are branches,
-// as the rejection is above.  Stopped tiles are skipped.
-template <bool MOMENTS>
-__global__ void accumulate_clamp_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G, float level,
-                                        float* __restrict__ sums, float* __restrict__ squares, uint32_t* __restrict__ kept,
-                                        uint32_t* __restrict__ clamped, float* __restrict__ lost,
-                                        const uint32_t* __restrict__ tile_stop) {
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t px, py;
-    if (!slot_pixel(G, slot, px, py)) return;
-    if (tile_stop && tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)] != 0) return;
-    float* S = sums + 3 * (size_t)slot;
-    float* Q = MOMENTS ? squares + 3 * (size_t)slot : nullptr;
-    float* D = lost + 3 * (size_t)slot;
-    V3 sum = v3(S[0], S[1], S[2]), sq = v3(0.0f, 0.0f, 0.0f), gone = v3(D[0], D[1], D[2]);
-    if (MOMENTS) sq = v3(Q[0], Q[1], Q[2]);
-    uint32_t k = kept[slot], n = clamped[slot];
+    if (CLAMP) gone = v3(D[0], D[1], D[2]);
+    uint32_t k = FINITE ? kept[slot] : 0u, n = CLAMP ? clamped[slot] : 0u;
     const float* c = colors + 3 * (size_t)slot;
     for (uint32_t s = 0; s < n_samples; ++s, c += 3 * (size_t)G.total) {
         V3 col = v3(c[0], c[1], c[2]);
-        if (!rtw_finite_sample(col.x, col.y, col.z)) continue;
-        const float m = rtw_clamp_max(rtw_clamp_max(col.x, col.y), col.z);
-        if (m > level) {
-            const float f = level / m;
-            const V3 cut = v3(rtw_clamp_min(col.x * f, level), rtw_clamp_min(col.y * f, level), rtw_clamp_min(col.z * f, level));
-            gone = add(gone, v3(col.x - cut.x, col.y - cut.y, col.z - cut.z));
-            col = cut;
-            ++n;
+        // (the rejection and the clamp are branches, not selects: the select form compiled to 52 B of scratch and ran
+        // the pass 4.5x slower, profiles/r12/pass_ab_select.txt)
+        if (FINITE && !rtw_finite_sample(col.x, col.y, col.z)) continue;
+        if (CLAMP) {
+            const float m = rtw_clamp_max(rtw_clamp_max(col.x, col.y), col.z);
+            if (m > level) {
+                const float f = level / m;
+                const V3 cut = v3(rtw_clamp_min(col.x * f, level), rtw_clamp_min(col.y * f, level), rtw_clamp_min(col.z * f, level));
+                gone = add(gone, v3(col.x - cut.x, col.y - cut.y, col.z - cut.z));
+                col = cut;
+                ++n;
+            }
         }
         sum = add(sum, col);
         if (MOMENTS) sq = add(sq, conv(col, col));
@@ -3451,11 +3399,31 @@ __global__ void accumulate_clamp_kernel(const float* __restrict__ colors, uint32
         Q[1] = sq.y;
         Q[2] = sq.z;
     }
-    D[0] = gone.x;
-    D[1] = gone.y;
-    D[2] = gone.z;
-    kept[slot] = k;
-    clamped[slot] = n;
+    if (CLAMP) {
+        D[0] = gone.x;
+        D[1] = gone.y;
+        D[2] = gone.z;
+        clamped[slot] = n;
+    }
+    if (FINITE) kept[slot] = k;
+}
+__global__ void accumulate_moments_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G,
+                                          float* __restrict__ sums, float* __restrict__ squares,
+                                          const uint32_t* __restrict__ tile_stop) {
+    accumulate_body<true, false, false>(colors, n_samples, G, 0.0f, sums, squares, nullptr, nullptr, nullptr, tile_stop);
+}
+template <bool MOMENTS>
+__global__ void accumulate_finite_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G,
+                                         float* __restrict__ sums, float* __restrict__ squares,
+                                         uint32_t* __restrict__ kept, const uint32_t* __restrict__ tile_stop) {
+    accumulate_body<MOMENTS, true, false>(colors, n_samples, G, 0.0f, sums, squares, kept, nullptr, nullptr, tile_stop);
+}
+template <bool MOMENTS>
+__global__ void accumulate_clamp_kernel(const float* __restrict__ colors, uint32_t n_samples, SlotGeom G, float level,
+                                        float* __restrict__ sums, float* __restrict__ squares, uint32_t* __restrict__ kept,
+                                        uint32_t* __restrict__ clamped, float* __restrict__ lost,
+                                        const uint32_t* __restrict__ tile_stop) {
+    accumulate_body<MOMENTS, true, true>(colors, n_samples, G, level, sums, squares, kept, clamped, lost, tile_stop);
 }
 // the standard error of a channel's mean from its sum and sum of squares (rtw.h: the order is the contract;
 // the arithmetic is rtw_adapt.h's, shared with the host)
@@ -3469,48 +3437,96 @@ __device__ __forceinline__ uint32_t slot_samples(const SlotGeom& G, uint32_t slo
     const uint32_t stop = tile_stop[slot / (uint32_t)(G.tile_w * G.tile_h)];
     return stop ? stop : samples;
 }
-// what 0: sum / samples (accumulate_kernel's last step); 1: the standard error (needs squares); 2: the sample
-// count itself, one uint32_t per pixel or slot (padding slots of a tile buffer: 0)
+// The resolves.  `what` numbers them across the three kernels: 0 the mean, 1 the standard error (needs squares), 2 the
+// sample counts, 3 kept, 4 clamped, 5 the clamp loss.  2, 3 and 4 are planes of one uint32_t per pixel or slot and share
+// resolve_count.  0, 1 and 5 are three floats per pixel or slot; their store stays written out in each kernel (as a
+// shared helper it compiled accum_resolve_finite_kernel to 32 VGPRs for 33 and accum_resolve_clamp_kernel to 16 for 25,
+// profiles/r21/resources.txt's bar is equality).
+// A slot's count n() (read for owned slots only) into its place; padding slots of a tile buffer: 0.
+template <class N>
+__device__ __forceinline__ void resolve_count(const SlotGeom& G, uint32_t slot, bool owned, int32_t px, int32_t py, N n,
+                                              float* out, int layout) {
+    uint32_t* o = (uint32_t*)out;
+    if (layout == RTW_LAYOUT_TILES) {
+        if (slot < G.total) o[slot] = owned ? n() : 0u;
+    } else if (owned) {
+        o[(size_t)py * G.width + px] = n();
+    }
+}
+// the standard error of the three channels of a slot that holds n samples
+__device__ __forceinline__ V3 slot_se(const float* S, const float* Q, uint32_t n) {
+    float m;
+    return v3(accum_se(S[0], Q[0], n, m), accum_se(S[1], Q[1], n, m), accum_se(S[2], Q[2], n, m));
+}
+// what 0: sum / samples (accumulate_kernel's last step); 1: the standard error; 2: the sample count itself
 __global__ void accum_resolve_kernel(const float* __restrict__ sums, const float* __restrict__ squares, SlotGeom G,
                                      uint32_t samples, const uint32_t* __restrict__ tile_stop, int what, float* out,
                                      int layout) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     int32_t px, py;
     const bool owned = slot_pixel(G, slot, px, py);
-    if (what == 2) {
-        uint32_t* o = (uint32_t*)out;
-        if (layout == RTW_LAYOUT_TILES) {
-            if (slot < G.total) o[slot] = owned ? slot_samples(G, slot, tile_stop, samples) : 0u;
-        } else if (owned) {
-            o[(size_t)py * G.width + px] = slot_samples(G, slot, tile_stop, samples);
-        }
-        return;
-    }
+    const auto count = [&] { return slot_samples(G, slot, tile_stop, samples); };
+    if (what == 2) return resolve_count(G, slot, owned, px, py, count, out, layout);
     if (!owned) return;
-    const uint32_t n = slot_samples(G, slot, tile_stop, samples);
+    const uint32_t n = count();
     const float* S = sums + 3 * (size_t)slot;
     V3 r;
-    if (what == 0) {
+    if (what == 0)
         r = divs(v3(S[0], S[1], S[2]), (float)n);
-    } else {
-        const float* Q = squares + 3 * (size_t)slot;
-        float m;
-        r = v3(accum_se(S[0], Q[0], n, m), accum_se(S[1], Q[1], n, m), accum_se(S[2], Q[2], n, m));
-    }
+    else
+        r = slot_se(S, squares + 3 * (size_t)slot, n);
     float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
     o[0] = r.x;
     o[1] = r.y;
     o[2] = r.z;
 }
+// An accumulator with RTW_ACCUM_FINITE: each pixel's own kept is its n.  what 0: sum / kept, +0 for kept == 0; 1: the
+// standard error with n = kept (not finite for kept < 2, rtw_finite.h); 3: kept itself.
+__global__ void accum_resolve_finite_kernel(const float* __restrict__ sums, const float* __restrict__ squares,
+                                            const uint32_t* __restrict__ kept, SlotGeom G, int what, float* out,
+                                            int layout) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    const bool owned = slot_pixel(G, slot, px, py);
+    if (what == 3) return resolve_count(G, slot, owned, px, py, [=] { return kept[slot]; }, out, layout);
+    if (!owned) return;
+    const uint32_t n = kept[slot];
+    const float* S = sums + 3 * (size_t)slot;
+    V3 r;
+    if (what == 0)
+        r = v3(rtw_finite_mean(S[0], n), rtw_finite_mean(S[1], n), rtw_finite_mean(S[2], n));
+    else
+        r = slot_se(S, squares + 3 * (size_t)slot, n);
+    float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
+    o[0] = r.x;
+    o[1] = r.y;
+    o[2] = r.z;
+}
+// An accumulator with RTW_ACCUM_CLAMP.  what 4: clamped itself; 5: lost / (float)kept per channel, +0 for kept == 0
+// (rtw_clamp_loss_mean).
+__global__ void accum_resolve_clamp_kernel(const float* __restrict__ lost, const uint32_t* __restrict__ kept,
+                                           const uint32_t* __restrict__ clamped, SlotGeom G, int what, float* out, int layout) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t px, py;
+    const bool owned = slot_pixel(G, slot, px, py);
+    if (what == 4) return resolve_count(G, slot, owned, px, py, [=] { return clamped[slot]; }, out, layout);
+    if (!owned) return;
+    const uint32_t n = kept[slot];
+    const float* D = lost + 3 * (size_t)slot;
+    float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
+    o[0] = rtw_clamp_loss_mean(D[0], n);
+    o[1] = rtw_clamp_loss_mean(D[1], n);
+    o[2] = rtw_clamp_loss_mean(D[2], n);
+}
 // rtw_accum_noise: per block the f64 sum of the finite per-pixel relative errors and their count, reduced
-// in a fixed tree order (the host adds the blocks in block order)
+// in a fixed tree order (the host adds the blocks in block order).  A pixel's n is its tile's sample count, or with
+// FINITE its own kept (its e is then NaN, and left out, for kept < 2).
 #define RTW_NOISE_BLOCK 256
-__global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const float* __restrict__ sums,
-                                                                      const float* __restrict__ squares, SlotGeom G,
-                                                                      uint32_t samples,
-                                                                      const uint32_t* __restrict__ tile_stop,
-                                                                      double* __restrict__ part_sum,
-                                                                      uint32_t* __restrict__ part_count) {
+template <bool FINITE>
+__device__ __forceinline__ void accum_noise_body(const float* __restrict__ sums, const float* __restrict__ squares,
+                                                 const uint32_t* __restrict__ kept, const SlotGeom& G, uint32_t samples,
+                                                 const uint32_t* __restrict__ tile_stop, double* __restrict__ part_sum,
+                                                 uint32_t* __restrict__ part_count) {
     __shared__ double sh_sum[RTW_NOISE_BLOCK];
     __shared__ uint32_t sh_cnt[RTW_NOISE_BLOCK];
     const uint32_t slot = blockIdx.x * RTW_NOISE_BLOCK + threadIdx.x;
@@ -3519,7 +3535,7 @@ __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const floa
     int32_t px, py;
     if (slot_pixel(G, slot, px, py)) {
         const float e = rtw_adapt_pixel(sums + 3 * (size_t)slot, squares + 3 * (size_t)slot,
-                                        slot_samples(G, slot, tile_stop, samples));
+                                        FINITE ? kept[slot] : slot_samples(G, slot, tile_stop, samples));
         if (rtw_adapt_finite(e)) {  // (false for NaN)
             v = (double)e;
             n = 1;
@@ -3540,140 +3556,33 @@ __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const floa
         part_count[blockIdx.x] = sh_cnt[0];
     }
 }
-// The resolves of an accumulator with RTW_ACCUM_FINITE (kernels of their own: the ones above compile as before).
-// what 0: sum / kept, +0 for kept == 0; 1: the standard error with n = kept (not finite for kept < 2, rtw_finite.h);
-// 3: kept itself, laid out and padded as what == 2 above lays out the sample counts.
-__global__ void accum_resolve_finite_kernel(const float* __restrict__ sums, const float* __restrict__ squares,
-                                            const uint32_t* __restrict__ kept, SlotGeom G, int what, float* out,
-                                            int layout) {
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t px, py;
-    const bool owned = slot_pixel(G, slot, px, py);
-    if (what == 3) {
-        uint32_t* o = (uint32_t*)out;
-        if (layout == RTW_LAYOUT_TILES) {
-            if (slot < G.total) o[slot] = owned ? kept[slot] : 0u;
-        } else if (owned) {
-            o[(size_t)py * G.width + px] = kept[slot];
-        }
-        return;
-    }
-    if (!owned) return;
-    const uint32_t n = kept[slot];
-    const float* S = sums + 3 * (size_t)slot;
-    V3 r;
-    if (what == 0) {
-        r = v3(rtw_finite_mean(S[0], n), rtw_finite_mean(S[1], n), rtw_finite_mean(S[2], n));
-    } else {
-        const float* Q = squares + 3 * (size_t)slot;
-        float m;
-        r = v3(accum_se(S[0], Q[0], n, m), accum_se(S[1], Q[1], n, m), accum_se(S[2], Q[2], n, m));
-    }
-    float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
-    o[0] = r.x;
-    o[1] = r.y;
-    o[2] = r.z;
+__global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_kernel(const float* __restrict__ sums,
+                                                                      const float* __restrict__ squares, SlotGeom G,
+                                                                      uint32_t samples,
+                                                                      const uint32_t* __restrict__ tile_stop,
+                                                                      double* __restrict__ part_sum,
+                                                                      uint32_t* __restrict__ part_count) {
+    accum_noise_body<false>(sums, squares, nullptr, G, samples, tile_stop, part_sum, part_count);
 }
-// The two resolves of an accumulator with RTW_ACCUM_CLAMP (a kernel of its own, as above).  what 4: clamped itself,
-// laid out and padded as kept is above; 5: lost / (float)kept per channel, +0 for kept == 0 (rtw_clamp_loss_mean).
-__global__ void accum_resolve_clamp_kernel(const float* __restrict__ lost, const uint32_t* __restrict__ kept,
-                                           const uint32_t* __restrict__ clamped, SlotGeom G, int what, float* out, int layout) {
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t px, py;
-    const bool owned = slot_pixel(G, slot, px, py);
-    if (what == 4) {
-        uint32_t* o = (uint32_t*)out;
-        if (layout == RTW_LAYOUT_TILES) {
-            if (slot < G.total) o[slot] = owned ? clamped[slot] : 0u;
-        } else if (owned) {
-            o[(size_t)py * G.width + px] = clamped[slot];
-        }
-        return;
-    }
-    if (!owned) return;
-    const uint32_t n = kept[slot];
-    const float* D = lost + 3 * (size_t)slot;
-    float* o = (layout == RTW_LAYOUT_TILES) ? out + 3 * (size_t)slot : out + 3 * ((size_t)py * G.width + px);
-    o[0] = rtw_clamp_loss_mean(D[0], n);
-    o[1] = rtw_clamp_loss_mean(D[1], n);
-    o[2] = rtw_clamp_loss_mean(D[2], n);
-}
-// accum_noise_kernel with each pixel's own kept as its n (the same fixed tree order)
 __global__ __launch_bounds__(RTW_NOISE_BLOCK) void accum_noise_finite_kernel(const float* __restrict__ sums,
                                                                              const float* __restrict__ squares,
                                                                              const uint32_t* __restrict__ kept, SlotGeom G,
                                                                              double* __restrict__ part_sum,
                                                                              uint32_t* __restrict__ part_count) {
-    __shared__ double sh_sum[RTW_NOISE_BLOCK];
-    __shared__ uint32_t sh_cnt[RTW_NOISE_BLOCK];
-    const uint32_t slot = blockIdx.x * RTW_NOISE_BLOCK + threadIdx.x;
-    double v = 0.0;
-    uint32_t n = 0;
-    int32_t px, py;
-    if (slot_pixel(G, slot, px, py)) {
-        const float e = rtw_adapt_pixel(sums + 3 * (size_t)slot, squares + 3 * (size_t)slot, kept[slot]);
-        if (rtw_adapt_finite(e)) {  // (false for NaN: every pixel with kept < 2)
-            v = (double)e;
-            n = 1;
-        }
-    }
-    sh_sum[threadIdx.x] = v;
-    sh_cnt[threadIdx.x] = n;
-    __syncthreads();
-    for (int step = RTW_NOISE_BLOCK / 2; step > 0; step >>= 1) {
-        if ((int)threadIdx.x < step) {
-            sh_sum[threadIdx.x] += sh_sum[threadIdx.x + step];
-            sh_cnt[threadIdx.x] += sh_cnt[threadIdx.x + step];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        part_sum[blockIdx.x] = sh_sum[0];
-        part_count[blockIdx.x] = sh_cnt[0];
-    }
+    accum_noise_body<true>(sums, squares, kept, G, 0u, nullptr, part_sum, part_count);
 }
 
 // ---- adaptive sampling (RTW_ACCUM_ADAPTIVE) ------------------------------------------
 // rtw_accum_adapt's tile test: one wave per local tile (RTW_ADAPT_BLOCK / 64 tiles per block; nothing depends
 // on which block runs where).  The lanes stride over the tile's slots, each keeps the maximum of its pixels'
 // finite e (rtw_adapt.h), a 64-lane butterfly maximum follows, and lane 0 stores the tile's stop.  Stopped
-// tiles are left alone.
+// tiles are left alone.  A pixel's n is the frontier `samples`, or with FINITE its own kept (rtw_finite.h); the stop
+// rule compares the frontier with min_samples either way.
 #define RTW_ADAPT_BLOCK 256
-__global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_kernel(const float* __restrict__ sums,
-                                                                      const float* __restrict__ squares,
-                                                                      rtw_adapt_geom G, uint32_t samples, float target,
-                                                                      uint32_t min_samples,
-                                                                      uint32_t* __restrict__ tile_stop) {
-    const int32_t lane = (int32_t)(threadIdx.x & 63u);
-    const int64_t lt64 = (int64_t)blockIdx.x * (RTW_ADAPT_BLOCK / 64) + (int64_t)(threadIdx.x >> 6);
-    if (lt64 >= (int64_t)G.local_tiles) return;  // wave-uniform
-    const int32_t lt = (int32_t)lt64;
-    if (tile_stop[lt] != 0) return;  // wave-uniform: a stopped tile stays stopped
-    const int32_t per_tile = G.tile_w * G.tile_h;
-    float E = rtw_adapt_none();
-    for (int32_t it = lane; it < per_tile; it += 64) {
-        int32_t px, py;
-        if (!rtw_adapt_slot_pixel(&G, lt, it, &px, &py)) continue;
-        const size_t at = 3 * ((size_t)lt * (size_t)per_tile + (size_t)it);
-        E = rtw_adapt_max(E, rtw_adapt_pixel(sums + at, squares + at, samples));
-    }
-    for (int off = 32; off > 0; off >>= 1) {  // every lane's E is finite or -inf: the maximum has no order
-        const float o = __shfl_xor(E, off, 64);
-        E = o > E ? o : E;
-    }
-    if (lane == 0) {
-        const uint32_t stop = rtw_adapt_stop(rtw_adapt_tile_e(E), samples, target, min_samples);
-        if (stop) tile_stop[lt] = stop;
-    }
-}
-// adapt_tiles_kernel for an accumulator with RTW_ACCUM_FINITE: each pixel's e from its own kept (rtw_finite.h);
-// the stop rule still compares the frontier `samples` with min_samples.
-__global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_finite_kernel(const float* __restrict__ sums,
-                                                                             const float* __restrict__ squares,
-                                                                             const uint32_t* __restrict__ kept,
-                                                                             rtw_adapt_geom G, uint32_t samples,
-                                                                             float target, uint32_t min_samples,
-                                                                             uint32_t* __restrict__ tile_stop) {
+template <bool FINITE>
+__device__ __forceinline__ void adapt_tiles_body(const float* __restrict__ sums, const float* __restrict__ squares,
+                                                 const uint32_t* __restrict__ kept, const rtw_adapt_geom& G, uint32_t samples,
+                                                 float target, uint32_t min_samples, uint32_t* __restrict__ tile_stop) {
     const int32_t lane = (int32_t)(threadIdx.x & 63u);
     const int64_t lt64 = (int64_t)blockIdx.x * (RTW_ADAPT_BLOCK / 64) + (int64_t)(threadIdx.x >> 6);
     if (lt64 >= (int64_t)G.local_tiles) return;  // wave-uniform
@@ -3685,7 +3594,7 @@ __global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_finite_kernel(con
         int32_t px, py;
         if (!rtw_adapt_slot_pixel(&G, lt, it, &px, &py)) continue;
         const size_t slot = (size_t)lt * (size_t)per_tile + (size_t)it;
-        E = rtw_adapt_max(E, rtw_adapt_pixel(sums + 3 * slot, squares + 3 * slot, kept[slot]));
+        E = rtw_adapt_max(E, rtw_adapt_pixel(sums + 3 * slot, squares + 3 * slot, FINITE ? kept[slot] : samples));
     }
     for (int off = 32; off > 0; off >>= 1) {  // every lane's E is finite or -inf: the maximum has no order
         const float o = __shfl_xor(E, off, 64);
@@ -3695,6 +3604,21 @@ __global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_finite_kernel(con
         const uint32_t stop = rtw_adapt_stop(rtw_adapt_tile_e(E), samples, target, min_samples);
         if (stop) tile_stop[lt] = stop;
     }
+}
+__global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_kernel(const float* __restrict__ sums,
+                                                                      const float* __restrict__ squares,
+                                                                      rtw_adapt_geom G, uint32_t samples, float target,
+                                                                      uint32_t min_samples,
+                                                                      uint32_t* __restrict__ tile_stop) {
+    adapt_tiles_body<false>(sums, squares, nullptr, G, samples, target, min_samples, tile_stop);
+}
+__global__ __launch_bounds__(RTW_ADAPT_BLOCK) void adapt_tiles_finite_kernel(const float* __restrict__ sums,
+                                                                             const float* __restrict__ squares,
+                                                                             const uint32_t* __restrict__ kept,
+                                                                             rtw_adapt_geom G, uint32_t samples,
+                                                                             float target, uint32_t min_samples,
+                                                                             uint32_t* __restrict__ tile_stop) {
+    adapt_tiles_body<true>(sums, squares, kept, G, samples, target, min_samples, tile_stop);
 }
 
 // The active tiles of `order` (null: 0, 1, 2, ...), in that order: a stable stream compaction by
@@ -5685,6 +5609,74 @@ int ensure_primary_lists(rtw_gpu_world* g, KArgs& A, hipStream_t stream) {
     return RTW_OK;
 }
 
+// The state arrays of an accumulator (rtw_accum), described once: one row per array, in the order of the packed
+// record's sections (rtw_parts_layout).  Creation, release, export, import, the pointer checks of the export / import
+// pairs and the record's sections all walk this table, so a new state array is one row here (and one in
+// progressive.py's _ARRAYS), plus the kernels that read it.
+enum { ACC_SUMS, ACC_SQUARES, ACC_KEPT, ACC_CLAMPED, ACC_LOST, ACC_STOP, ACC_ARRAYS };
+struct AccumArrayDesc {
+    uint32_t flag;          // the flag that calls for the array (0: every accumulator holds it)
+    uint32_t words;         // 32-bit words per slot, or per local tile
+    bool per_tile, f32;     // one entry per tile, not per slot; float, not uint32_t
+    const char* name;       // in messages
+    const char* flag_name;  // in messages
+};
+constexpr AccumArrayDesc ACC_DESC[ACC_ARRAYS] = {{0u, 3, false, true, "sums", ""},
+                                                 {RTW_ACCUM_MOMENTS, 3, false, true, "squares", "RTW_ACCUM_MOMENTS"},
+                                                 {RTW_ACCUM_FINITE, 1, false, false, "kept", "RTW_ACCUM_FINITE"},
+                                                 {RTW_ACCUM_CLAMP, 1, false, false, "clamped", "RTW_ACCUM_CLAMP"},
+                                                 {RTW_ACCUM_CLAMP, 3, false, true, "lost", "RTW_ACCUM_CLAMP"},
+                                                 {RTW_ACCUM_ADAPTIVE, 1, true, false, "tile_stop", "RTW_ACCUM_ADAPTIVE"}};
+// the device pointers, owned by the accumulator (null: the flags do not call for the array); padding slots stay zero
+struct AccumArrays {
+    void* d[ACC_ARRAYS] = {};
+    template <int I>
+    std::conditional_t<ACC_DESC[I].f32, float, uint32_t>* get() const {
+        return (std::conditional_t<ACC_DESC[I].f32, float, uint32_t>*)d[I];
+    }
+};
+struct AccumRun {
+    const AccumArrays* arrays;
+    float level;    // RTW_ACCUM_CLAMP: the level (else 0)
+    uint32_t base;  // samples the sums already hold
+    // adaptive accumulators with a stopped tile (else null / 0): the stop map, the buffer for the compacted
+    // tile order (local tiles + 1 entries: the list, then its length) and the active tiles K (host's count)
+    const uint32_t* tile_stop = nullptr;
+    uint32_t* active_perm = nullptr;
+    uint32_t active = 0;
+    // an accumulator with moments or kept counts sees its samples one by one, in the accumulate pass
+    bool per_sample() const { return arrays->d[ACC_SQUARES] || arrays->d[ACC_KEPT]; }
+};
+SlotGeom accum_geom(const KArgs& A) {
+    return SlotGeom{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
+}
+// An accumulator's add pass over the `n_samples` colours of a launch: the instantiation of accumulate_body its arrays
+// call for; without moments and kept counts, the one-shot frames' kernel as a middle launch (onto the sums, no division).
+void launch_accumulate(const AccumRun& acc, const KArgs& A, const float* colors, uint32_t n_samples, hipStream_t stream) {
+    const dim3 grid((A.total + 255) / 256), block(256);
+    const SlotGeom G = accum_geom(A);
+    const AccumArrays& S = *acc.arrays;
+    float *sums = S.get<ACC_SUMS>(), *squares = S.get<ACC_SQUARES>(), *lost = S.get<ACC_LOST>();
+    uint32_t *kept = S.get<ACC_KEPT>(), *clamped = S.get<ACC_CLAMPED>();
+    if (clamped && squares)
+        hipLaunchKernelGGL(accumulate_clamp_kernel<true>, grid, block, 0, stream, colors, n_samples, G, acc.level, sums, squares,
+                           kept, clamped, lost, acc.tile_stop);
+    else if (clamped)
+        hipLaunchKernelGGL(accumulate_clamp_kernel<false>, grid, block, 0, stream, colors, n_samples, G, acc.level, sums, squares,
+                           kept, clamped, lost, acc.tile_stop);
+    else if (kept && squares)
+        hipLaunchKernelGGL(accumulate_finite_kernel<true>, grid, block, 0, stream, colors, n_samples, G, sums, squares, kept,
+                           acc.tile_stop);
+    else if (kept)
+        hipLaunchKernelGGL(accumulate_finite_kernel<false>, grid, block, 0, stream, colors, n_samples, G, sums, squares, kept,
+                           acc.tile_stop);
+    else if (squares)
+        hipLaunchKernelGGL(accumulate_moments_kernel, grid, block, 0, stream, colors, n_samples, G, sums, squares, acc.tile_stop);
+    else
+        hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, stream, colors, n_samples, A.total, sums, 0, 0, A.spp, (float*)nullptr,
+                           A.layout, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count);
+}
+
 // One frame: launches of at most RTW_SAMPLE_BUFFER_BYTES (default: half of the HBM this world could
 // use, at most 64 GiB) of per-sample colours,
 // each followed by the in-order accumulation; work items of RTW_CHUNK (default 1) samples.
@@ -5692,21 +5684,6 @@ int ensure_primary_lists(rtw_gpu_world* g, KArgs& A, hipStream_t stream) {
 // world's counters, so a progress poller can read how many items each launch has handed out.
 // An accumulator's add (rtw_accum_add) runs through the same body: samples [base, base + A.spp) onto
 // the accumulator's own sums (and squares), no final division, nothing of the world's running buffer.
-struct AccumRun {
-    float* sums;
-    float* squares;  // null: no moments
-    uint32_t base;   // samples the sums already hold
-    // adaptive accumulators with a stopped tile (else null / 0): the stop map, the buffer for the compacted
-    // tile order (local tiles + 1 entries: the list, then its length) and the active tiles K (host's count)
-    const uint32_t* tile_stop = nullptr;
-    uint32_t* active_perm = nullptr;
-    uint32_t active = 0;
-    uint32_t* kept = nullptr;  // RTW_ACCUM_FINITE: the per-slot kept counts (else null)
-    // RTW_ACCUM_CLAMP: the per-slot clamped counts, lost sums and the level (else null / 0)
-    uint32_t* clamped = nullptr;
-    float* lost = nullptr;
-    float level = 0.0f;
-};
 int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStream_t stream,
                       std::vector<uint64_t>* launch_items, const AccumRun* acc, bool acc_allow_wp = true);
 
@@ -5743,7 +5720,7 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
     // (... nor one whose world takes a GEN kernel: launch_render's RTW_ACC_NO_WP, render_frame)
     // ... nor one with RTW_ACCUM_FINITE: its filter sees the samples one by one in the accumulate pass, and a
     // whole-pixel launch sums inside the render kernel
-    if (!stats && A.thread_count <= 1 && !(acc && (acc->squares || acc->kept || !acc_allow_wp))) {
+    if (!stats && A.thread_count <= 1 && !(acc && (acc->per_sample() || !acc_allow_wp))) {
         const uint64_t lanes = (uint64_t)std::max(1, g->cus) * RTW_BLOCK;
         const char* wp = std::getenv("RTW_WHOLE_PIXEL");
         if (wp && wp[0] == '1') A.whole_pixel = 1;
@@ -5870,7 +5847,7 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         if (acc && A.whole_pixel) {  // the lanes continue the accumulator's sums (KArgs::whole_pixel)
             KArgs B = A;
             B.spp = 1;
-            B.out = acc->sums;
+            B.out = acc->arrays->get<ACC_SUMS>();
             B.layout = RTW_LAYOUT_TILES;
             rc = launch_render(g, B, LK_RENDER, stream, true);
             if (rc == RTW_ACC_NO_WP && launch_items) launch_items->pop_back();
@@ -5881,32 +5858,8 @@ int render_frame_body(rtw_gpu_world* g, KArgs& A, bool stats, float* out, hipStr
         const unsigned blocks = (A.total + 255) / 256;
         if (A.whole_pixel) {
             // the render kernel wrote the pixels
-        } else if (acc && acc->clamped) {
-            const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
-            if (acc->squares)
-                hipLaunchKernelGGL(accumulate_clamp_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
-                                   s1 - s0, G, acc->level, acc->sums, acc->squares, acc->kept, acc->clamped, acc->lost,
-                                   acc->tile_stop);
-            else
-                hipLaunchKernelGGL(accumulate_clamp_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
-                                   s1 - s0, G, acc->level, acc->sums, (float*)nullptr, acc->kept, acc->clamped, acc->lost,
-                                   acc->tile_stop);
-        } else if (acc && acc->kept) {
-            const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
-            if (acc->squares)
-                hipLaunchKernelGGL(accumulate_finite_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
-                                   s1 - s0, G, acc->sums, acc->squares, acc->kept, acc->tile_stop);
-            else
-                hipLaunchKernelGGL(accumulate_finite_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
-                                   s1 - s0, G, acc->sums, (float*)nullptr, acc->kept, acc->tile_stop);
-        } else if (acc && acc->squares) {
-            const SlotGeom G{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
-            hipLaunchKernelGGL(accumulate_moments_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
-                               s1 - s0, G, acc->sums, acc->squares, acc->tile_stop);
-        } else if (acc) {  // the one-shot frames' kernel as a middle launch: onto the sums, no division
-            hipLaunchKernelGGL(accumulate_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors, s1 - s0,
-                               A.total, acc->sums, 0, 0, A.spp, out, A.layout, A.width, A.height, A.tile_w, A.tile_h,
-                               A.tiles_x, A.part_index, A.part_count);
+        } else if (acc) {
+            launch_accumulate(*acc, A, g->colors, s1 - s0, stream);
         } else if (n_planes > 1 && !plane_buffer)
             hipLaunchKernelGGL(merge_planes_direct_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g->colors,
                                A.total, n_planes, whole, rem, out, A.layout, A.width, A.height, A.tile_w, A.tile_h,
@@ -5972,49 +5925,38 @@ struct rtw_accum {
     rtw_gpu_world* g = nullptr;
     rtw_render_params p{};  // samples_per_pixel: set per add
     rtw_accum_info info{};
-    float* sums = nullptr;     // 3 floats per slot, owned; padding slots stay zero
-    float* squares = nullptr;  // the same with RTW_ACCUM_MOMENTS, else null
-    uint32_t* kept = nullptr;  // RTW_ACCUM_FINITE: one count per slot (padding slots stay zero), else null
-    // RTW_ACCUM_CLAMP: one clamped count and three lost floats per slot (padding slots stay zero), else null; the level
-    uint32_t* clamped = nullptr;
-    float* lost = nullptr;
-    float level = 0.0f;
+    AccumArrays st;      // the state arrays (ACC_DESC)
+    float level = 0.0f;  // RTW_ACCUM_CLAMP: the level
     double* noise_sum = nullptr;  // rtw_accum_noise: per-block partials (device), grown on first use
     uint32_t* noise_cnt = nullptr;
-    // RTW_ACCUM_ADAPTIVE: the stop map, the compacted tile order of the adds (tiles + 1
-    // entries), the host's copy of the map (kept current by adapt and import: the adds' K) and its zeros
-    uint32_t* tile_stop = nullptr;
+    // RTW_ACCUM_ADAPTIVE, beside the stop map st.d[ACC_STOP]: the compacted tile order of the adds
+    // (tiles + 1 entries), the host's copy of the map (kept current by adapt and import: the adds' K) and its zeros
     uint32_t* active_perm = nullptr;
     std::vector<uint32_t> h_stop;
     uint32_t tiles = 0, active = 0;
+    // the bytes array i holds: its words per slot or per local tile
+    size_t bytes(int i) const {
+        return (ACC_DESC[i].per_tile ? (size_t)tiles : (size_t)info.slots) * ACC_DESC[i].words * sizeof(uint32_t);
+    }
 };
 
 // The world went first (rtw_world_release): the accumulator's device state goes with it, and every later
 // call on it but rtw_accum_get_info and rtw_accum_release is refused.
 static void accum_orphan(rtw_accum* a) {
-    if (a->sums) (void)hipFree(a->sums);
-    if (a->squares) (void)hipFree(a->squares);
-    if (a->kept) (void)hipFree(a->kept);
-    if (a->clamped) (void)hipFree(a->clamped);
-    if (a->lost) (void)hipFree(a->lost);
+    for (void*& d : a->st.d) {
+        if (d) (void)hipFree(d);
+        d = nullptr;
+    }
     if (a->noise_sum) (void)hipFree(a->noise_sum);
     if (a->noise_cnt) (void)hipFree(a->noise_cnt);
-    if (a->tile_stop) (void)hipFree(a->tile_stop);
     if (a->active_perm) (void)hipFree(a->active_perm);
-    a->tile_stop = a->active_perm = nullptr;
-    a->sums = a->squares = nullptr;
-    a->kept = nullptr;
-    a->clamped = nullptr;
-    a->lost = nullptr;
+    a->active_perm = nullptr;
     a->noise_sum = nullptr;
     a->noise_cnt = nullptr;
     a->g = nullptr;
 }
 
 namespace {
-SlotGeom accum_geom(const KArgs& A) {
-    return SlotGeom{A.total, A.width, A.height, A.tile_w, A.tile_h, A.tiles_x, A.part_index, A.part_count};
-}
 // the accumulator's launch arguments for `spp` samples (geometry checks as for a one-shot frame)
 int accum_args(const rtw_accum* a, uint32_t spp, KArgs& A) {
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
@@ -6040,12 +5982,14 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
     if (!a || !d_out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     if (what == 0 && a->info.samples < 1) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "resolve needs samples >= 1");
-    if (what == 1 && !a->squares)
+    const float *sums = a->st.get<ACC_SUMS>(), *squares = a->st.get<ACC_SQUARES>(), *lost = a->st.get<ACC_LOST>();
+    const uint32_t *kept = a->st.get<ACC_KEPT>(), *clamped = a->st.get<ACC_CLAMPED>(), *tile_stop = a->st.get<ACC_STOP>();
+    if (what == 1 && !squares)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs an accumulator with RTW_ACCUM_MOMENTS");
     if (what == 1 && a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the standard error needs samples >= 2");
     // (what == 2, the sample counts: any accumulator at any point; a fresh one holds 0 everywhere)
-    if (what == 3 && !a->kept) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the kept counts need an accumulator with RTW_ACCUM_FINITE");
-    if (what >= 4 && !a->clamped)
+    if (what == 3 && !kept) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the kept counts need an accumulator with RTW_ACCUM_FINITE");
+    if (what >= 4 && !clamped)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the clamped counts and the clamp loss need an accumulator with RTW_ACCUM_CLAMP");
     KArgs A;
     int rc = accum_args(a, 1, A);
@@ -6053,17 +5997,16 @@ int accum_resolve(rtw_accum* a, float* d_out, hipStream_t stream, int what) {
     if (A.total == 0) return RTW_OK;
     rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
+    const dim3 grid((A.total + 255) / 256), block(256);
     if (what >= 4)
-        hipLaunchKernelGGL(accum_resolve_clamp_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream, (const float*)a->lost,
-                           (const uint32_t*)a->kept, (const uint32_t*)a->clamped, accum_geom(A), what, d_out, A.layout);
-    else if (a->kept && what != 2)  // a finite accumulator divides by the pixel's own kept
-        hipLaunchKernelGGL(accum_resolve_finite_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream,
-                           (const float*)a->sums, (const float*)a->squares, (const uint32_t*)a->kept, accum_geom(A), what,
-                           d_out, A.layout);
+        hipLaunchKernelGGL(accum_resolve_clamp_kernel, grid, block, 0, stream, lost, kept, clamped, accum_geom(A), what, d_out,
+                           A.layout);
+    else if (kept && what != 2)  // a finite accumulator divides by the pixel's own kept
+        hipLaunchKernelGGL(accum_resolve_finite_kernel, grid, block, 0, stream, sums, squares, kept, accum_geom(A), what, d_out,
+                           A.layout);
     else
-        hipLaunchKernelGGL(accum_resolve_kernel, dim3((A.total + 255) / 256), dim3(256), 0, stream, (const float*)a->sums,
-                           (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop, what,
-                           d_out, A.layout);
+        hipLaunchKernelGGL(accum_resolve_kernel, grid, block, 0, stream, sums, squares, accum_geom(A), a->info.samples, tile_stop,
+                           what, d_out, A.layout);
     HIP_TRY(hipGetLastError());
     return accum_leave(a, stream);
 }
@@ -6111,18 +6054,15 @@ static int accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t f
     I.world_fingerprint = g->fingerprint;
     I.slots = (int64_t)A.total;
     (void)hipSetDevice(g->device);
-    const size_t bytes = std::max<size_t>(16, (size_t)A.total * 3 * sizeof(float));
-    hipError_t e = hipMalloc(&a->sums, bytes);
-    if (e == hipSuccess && (flags & RTW_ACCUM_MOMENTS)) e = hipMalloc(&a->squares, bytes);
-    const size_t kept_bytes = std::max<size_t>(16, (size_t)A.total * sizeof(uint32_t));
-    if (e == hipSuccess && (flags & RTW_ACCUM_FINITE)) e = hipMalloc(&a->kept, kept_bytes);
-    if (e == hipSuccess && (flags & RTW_ACCUM_CLAMP)) e = hipMalloc(&a->clamped, kept_bytes);
-    if (e == hipSuccess && (flags & RTW_ACCUM_CLAMP)) e = hipMalloc(&a->lost, bytes);
     a->tiles = a->active = A.total / (uint32_t)(A.tile_w * A.tile_h);
+    // what array i is allocated with: at least 16 bytes; the stop map one entry more, as the compacted order beside it
     const size_t stop_bytes = ((size_t)a->tiles + 1) * sizeof(uint32_t);
+    auto room = [&](int i) { return i == ACC_STOP ? stop_bytes : std::max<size_t>(16, a->bytes(i)); };
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < ACC_ARRAYS; ++i)
+        if (e == hipSuccess && (ACC_DESC[i].flag == 0u || (flags & ACC_DESC[i].flag))) e = hipMalloc(&a->st.d[i], room(i));
     if (flags & RTW_ACCUM_ADAPTIVE) {
         a->h_stop.assign(a->tiles, 0u);
-        if (e == hipSuccess) e = hipMalloc(&a->tile_stop, stop_bytes);
         if (e == hipSuccess) e = hipMalloc(&a->active_perm, stop_bytes);
     }
     if (e != hipSuccess) {
@@ -6130,12 +6070,8 @@ static int accum_create(rtw_gpu_world* g, const rtw_render_params* p, uint32_t f
         return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
     }
     // (synchronous: the zeros are there before any stream's first add)
-    e = hipMemset(a->sums, 0, bytes);
-    if (e == hipSuccess && a->squares) e = hipMemset(a->squares, 0, bytes);
-    if (e == hipSuccess && a->kept) e = hipMemset(a->kept, 0, kept_bytes);
-    if (e == hipSuccess && a->clamped) e = hipMemset(a->clamped, 0, kept_bytes);
-    if (e == hipSuccess && a->lost) e = hipMemset(a->lost, 0, bytes);
-    if (e == hipSuccess && a->tile_stop) e = hipMemset(a->tile_stop, 0, stop_bytes);
+    for (int i = 0; i < ACC_ARRAYS; ++i)
+        if (e == hipSuccess && a->st.d[i]) e = hipMemset(a->st.d[i], 0, room(i));
     if (e == hipSuccess && a->active_perm) e = hipMemset(a->active_perm, 0, stop_bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
@@ -6186,16 +6122,13 @@ extern "C" RTW_API int rtw_accum_add(rtw_accum* a, uint32_t n, void* stream) {
     KArgs A;
     const int v = accum_args(a, n, A);
     if (v != RTW_OK) return v;
-    if (a->tile_stop && a->active == 0) return RTW_OK;  // adaptive, every tile stopped: nothing to render
+    const uint32_t* tile_stop = a->st.get<ACC_STOP>();
+    if (tile_stop && a->active == 0) return RTW_OK;  // adaptive, every tile stopped: nothing to render
     A.out = nullptr;  // an add writes the accumulator's state only
     HIP_TRY(hipSetDevice(a->g->device));
-    AccumRun run{a->sums, a->squares, a->info.samples};
-    run.kept = a->kept;
-    run.clamped = a->clamped;
-    run.lost = a->lost;
-    run.level = a->level;
-    if (a->tile_stop && a->active < a->tiles) {  // (all active: exactly a plain moments accumulator's add)
-        run.tile_stop = a->tile_stop;
+    AccumRun run{&a->st, a->level, a->info.samples};
+    if (tile_stop && a->active < a->tiles) {  // (all active: exactly a plain moments accumulator's add)
+        run.tile_stop = tile_stop;
         run.active_perm = a->active_perm;
         run.active = a->active;
     }
@@ -6216,7 +6149,9 @@ extern "C" RTW_API int rtw_accum_resolve_stderr(rtw_accum* a, float* d_out, void
 extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* noise, int64_t* pixels_counted) {
     if (!a || !noise || !pixels_counted) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
-    if (!a->squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the noise estimate needs an accumulator with RTW_ACCUM_MOMENTS");
+    const float *sums = a->st.get<ACC_SUMS>(), *squares = a->st.get<ACC_SQUARES>();
+    const uint32_t *kept = a->st.get<ACC_KEPT>(), *tile_stop = a->st.get<ACC_STOP>();
+    if (!squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the noise estimate needs an accumulator with RTW_ACCUM_MOMENTS");
     if (a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the noise estimate needs samples >= 2");
     hipStream_t stream = (hipStream_t)stream_;
     KArgs A;
@@ -6232,13 +6167,12 @@ extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* nois
         HIP_TRY(hipMalloc(&a->noise_sum, (size_t)blocks * sizeof(double)));
         HIP_TRY(hipMalloc(&a->noise_cnt, (size_t)blocks * sizeof(uint32_t)));
     }
-    if (a->kept)
-        hipLaunchKernelGGL(accum_noise_finite_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, (const float*)a->sums,
-                           (const float*)a->squares, (const uint32_t*)a->kept, accum_geom(A), a->noise_sum, a->noise_cnt);
+    if (kept)
+        hipLaunchKernelGGL(accum_noise_finite_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, sums, squares, kept,
+                           accum_geom(A), a->noise_sum, a->noise_cnt);
     else
-        hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, (const float*)a->sums,
-                           (const float*)a->squares, accum_geom(A), a->info.samples, (const uint32_t*)a->tile_stop,
-                           a->noise_sum, a->noise_cnt);
+        hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(RTW_NOISE_BLOCK), 0, stream, sums, squares, accum_geom(A),
+                           a->info.samples, tile_stop, a->noise_sum, a->noise_cnt);
     HIP_TRY(hipGetLastError());
     rc = accum_leave(a, stream);
     if (rc != RTW_OK) return rc;
@@ -6259,21 +6193,27 @@ extern "C" RTW_API int rtw_accum_noise(rtw_accum* a, void* stream_, double* nois
 }
 
 namespace {
-int accum_export(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop, uint32_t* host_kept = nullptr,
-                 uint32_t* host_clamped = nullptr, float* host_lost = nullptr) {
-    if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
+// The host arrays of an export or import call, by the table's rows (null: not given).  The arguments come in the order
+// of the C ABI's pairs: sums, squares, tile_stop, kept, clamped, lost.
+struct HostArrays {
+    void* p[ACC_ARRAYS];
+    HostArrays(const void* sums, const void* squares, const void* stop = nullptr, const void* kept = nullptr,
+               const void* clamped = nullptr, const void* lost = nullptr) {
+        const void* by_row[ACC_ARRAYS] = {sums, squares, kept, clamped, lost, stop};
+        for (int i = 0; i < ACC_ARRAYS; ++i) p[i] = const_cast<void*>(by_row[i]);  // (an import only reads them)
+    }
+};
+
+int accum_export(rtw_accum* a, const HostArrays& host) {
+    if (!a || !host.p[ACC_SUMS]) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
-    if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
+    if (a->st.d[ACC_SQUARES] && !host.p[ACC_SQUARES])
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
     HIP_TRY(hipSetDevice(a->g->device));
     if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
-    const size_t bytes = (size_t)a->info.slots * 3 * sizeof(float);
-    if (bytes == 0) return RTW_OK;
-    HIP_TRY(hipMemcpy(host_sums, a->sums, bytes, hipMemcpyDeviceToHost));
-    if (a->squares) HIP_TRY(hipMemcpy(host_squares, a->squares, bytes, hipMemcpyDeviceToHost));
-    if (host_stop) HIP_TRY(hipMemcpy(host_stop, a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (host_kept) HIP_TRY(hipMemcpy(host_kept, a->kept, (size_t)a->info.slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (host_clamped) HIP_TRY(hipMemcpy(host_clamped, a->clamped, (size_t)a->info.slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (host_lost) HIP_TRY(hipMemcpy(host_lost, a->lost, bytes, hipMemcpyDeviceToHost));
+    if (a->info.slots == 0) return RTW_OK;
+    for (int i = 0; i < ACC_ARRAYS; ++i)
+        if (host.p[i] && a->st.d[i]) HIP_TRY(hipMemcpy(host.p[i], a->st.d[i], a->bytes(i), hipMemcpyDeviceToHost));
     return RTW_OK;
 }
 
@@ -6291,28 +6231,27 @@ int refuse_clamp(const rtw_accum* a, const char* call) {
                                                    "clamped and lost: use rtw_accum_export_state_clamp / rtw_accum_import_state_clamp");
 }
 
-// rtw_accum_export_state / rtw_accum_import_state: a pointer the flags call for is non-null, any other is null
-int state_pointers(const rtw_accum* a, const void* squares, const void* stop, const void* kept) {
-    const struct {
-        uint32_t flag;
-        const void* p;
-        const char* name;
-        const char* flag_name;
-    } want[3] = {{RTW_ACCUM_MOMENTS, squares, "squares", "RTW_ACCUM_MOMENTS"},
-                 {RTW_ACCUM_ADAPTIVE, stop, "tile_stop", "RTW_ACCUM_ADAPTIVE"},
-                 {RTW_ACCUM_FINITE, kept, "kept", "RTW_ACCUM_FINITE"}};
-    for (const auto& w : want) {
+// The state pairs (rtw_accum_export_state / rtw_accum_import_state and the clamp pair): a pointer the flags call for is
+// non-null, any other is null.  The arrays are checked in the order of the pairs' arguments; the clamp pair first
+// wants the flag itself.
+int state_pointers(const rtw_accum* a, const HostArrays& host, bool clamp_pair) {
+    if (clamp_pair && !(a->info.flags & RTW_ACCUM_CLAMP))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator has no RTW_ACCUM_CLAMP: use rtw_accum_export_state / rtw_accum_import_state");
+    for (int i : {ACC_SQUARES, ACC_STOP, ACC_KEPT, ACC_CLAMPED, ACC_LOST}) {
+        const AccumArrayDesc& w = ACC_DESC[i];
         const bool has = (a->info.flags & w.flag) != 0;
-        if (has && !w.p) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("null ") + w.name + " (the accumulator has " + w.flag_name + ")");
-        if (!has && w.p)
+        if (has && !host.p[i])
+            return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("null ") + w.name + " (the accumulator has " + w.flag_name + ")");
+        if (!has && host.p[i])
             return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(w.name) + " given, but the accumulator has no " + w.flag_name);
     }
     return RTW_OK;
 }
 
-int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums, const float* host_squares,
-                 const uint32_t* host_stop, const uint32_t* host_kept = nullptr, const uint32_t* host_clamped = nullptr,
-                 const float* host_lost = nullptr) {
+int accum_import(rtw_accum* a, const rtw_accum_info* info, const HostArrays& host) {
+    const float *host_sums = (const float*)host.p[ACC_SUMS], *host_lost = (const float*)host.p[ACC_LOST];
+    const uint32_t *host_stop = (const uint32_t*)host.p[ACC_STOP], *host_kept = (const uint32_t*)host.p[ACC_KEPT],
+                   *host_clamped = (const uint32_t*)host.p[ACC_CLAMPED];
     if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     const rtw_accum_info& M = a->info;
@@ -6333,11 +6272,12 @@ int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sum
     if (info->world_fingerprint != M.world_fingerprint) return differs("world_fingerprint");
     if (info->slots != M.slots) return differs("slots");
     if ((M.flags & RTW_ACCUM_CLAMP) && info->reserved != M.reserved) return differs("clamp (the level, info.reserved)");
-    if (a->squares && !host_squares) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
-    if (a->tile_stop && !host_stop)
+    if (a->st.d[ACC_SQUARES] && !host.p[ACC_SQUARES])
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null squares (the accumulator keeps moments)");
+    if (a->st.d[ACC_STOP] && !host_stop)
         return rtw::fail(RTW_ERR_INVALID_ARGUMENT,
                          "an adaptive accumulator's state includes tile_stop: import it with rtw_accum_import_adaptive");
-    if (!a->tile_stop && host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "tile_stop given, but the accumulator is not adaptive");
+    if (!a->st.d[ACC_STOP] && host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "tile_stop given, but the accumulator is not adaptive");
     uint32_t active = a->tiles;
     if (host_stop) {
         active = 0;
@@ -6382,15 +6322,8 @@ int accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sum
     }
     HIP_TRY(hipSetDevice(a->g->device));
     if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
-    const size_t bytes = (size_t)M.slots * 3 * sizeof(float);
-    if (bytes > 0) {
-        HIP_TRY(hipMemcpy(a->sums, host_sums, bytes, hipMemcpyHostToDevice));
-        if (a->squares) HIP_TRY(hipMemcpy(a->squares, host_squares, bytes, hipMemcpyHostToDevice));
-        if (host_stop) HIP_TRY(hipMemcpy(a->tile_stop, host_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (host_kept) HIP_TRY(hipMemcpy(a->kept, host_kept, (size_t)M.slots * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (host_clamped) HIP_TRY(hipMemcpy(a->clamped, host_clamped, (size_t)M.slots * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (host_lost) HIP_TRY(hipMemcpy(a->lost, host_lost, bytes, hipMemcpyHostToDevice));
-    }
+    for (int i = 0; M.slots > 0 && i < ACC_ARRAYS; ++i)
+        if (host.p[i] && a->st.d[i]) HIP_TRY(hipMemcpy(a->st.d[i], host.p[i], a->bytes(i), hipMemcpyHostToDevice));
     if (host_stop) a->h_stop.assign(host_stop, host_stop + a->tiles);
     a->active = active;
     a->info.samples = info->samples;
@@ -6409,27 +6342,27 @@ int64_t tile_pixels(const rtw_accum_info& I, uint32_t lt) {
 
 extern "C" RTW_API int rtw_accum_export(rtw_accum* a, float* host_sums, float* host_squares) {
     if (refuse_clamp(a, "rtw_accum_export") != RTW_OK || refuse_finite(a, "rtw_accum_export") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
-    return accum_export(a, host_sums, host_squares, nullptr);
+    return accum_export(a, HostArrays(host_sums, host_squares));
 }
 
 extern "C" RTW_API int rtw_accum_import(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                         const float* host_squares) {
     if (refuse_clamp(a, "rtw_accum_import") != RTW_OK || refuse_finite(a, "rtw_accum_import") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
-    return accum_import(a, info, host_sums, host_squares, nullptr);
+    return accum_import(a, info, HostArrays(host_sums, host_squares));
 }
 
 extern "C" RTW_API int rtw_accum_export_adaptive(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop) {
     if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (refuse_clamp(a, "rtw_accum_export_adaptive") != RTW_OK || refuse_finite(a, "rtw_accum_export_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
-    if (a->g && !a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
-    return accum_export(a, host_sums, host_squares, host_stop);
+    if (a->g && !a->st.d[ACC_STOP]) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
+    return accum_export(a, HostArrays(host_sums, host_squares, host_stop));
 }
 
 extern "C" RTW_API int rtw_accum_import_adaptive(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
                                                  const float* host_squares, const uint32_t* host_stop) {
     if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (refuse_clamp(a, "rtw_accum_import_adaptive") != RTW_OK || refuse_finite(a, "rtw_accum_import_adaptive") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
-    return accum_import(a, info, host_sums, host_squares, host_stop);
+    return accum_import(a, info, HostArrays(host_sums, host_squares, host_stop));
 }
 
 extern "C" RTW_API int rtw_accum_export_state(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop,
@@ -6437,8 +6370,9 @@ extern "C" RTW_API int rtw_accum_export_state(rtw_accum* a, float* host_sums, fl
     if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     if (refuse_clamp(a, "rtw_accum_export_state") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
-    const int rc = state_pointers(a, host_squares, host_stop, host_kept);
-    return rc != RTW_OK ? rc : accum_export(a, host_sums, host_squares, host_stop, host_kept);
+    const HostArrays host(host_sums, host_squares, host_stop, host_kept);
+    const int rc = state_pointers(a, host, false);
+    return rc != RTW_OK ? rc : accum_export(a, host);
 }
 
 extern "C" RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
@@ -6447,29 +6381,18 @@ extern "C" RTW_API int rtw_accum_import_state(rtw_accum* a, const rtw_accum_info
     if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
     if (refuse_clamp(a, "rtw_accum_import_state") != RTW_OK) return RTW_ERR_INVALID_ARGUMENT;
-    const int rc = state_pointers(a, host_squares, host_stop, host_kept);
-    return rc != RTW_OK ? rc : accum_import(a, info, host_sums, host_squares, host_stop, host_kept);
+    const HostArrays host(host_sums, host_squares, host_stop, host_kept);
+    const int rc = state_pointers(a, host, false);
+    return rc != RTW_OK ? rc : accum_import(a, info, host);
 }
-
-namespace {
-// the clamp pair's own two pointers, after state_pointers' rule for the other four
-int clamp_pointers(const rtw_accum* a, const void* squares, const void* stop, const void* kept, const void* clamped, const void* lost) {
-    if (!(a->info.flags & RTW_ACCUM_CLAMP))
-        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator has no RTW_ACCUM_CLAMP: use rtw_accum_export_state / rtw_accum_import_state");
-    const int rc = state_pointers(a, squares, stop, kept);
-    if (rc != RTW_OK) return rc;
-    if (!clamped) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null clamped (the accumulator has RTW_ACCUM_CLAMP)");
-    if (!lost) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null lost (the accumulator has RTW_ACCUM_CLAMP)");
-    return RTW_OK;
-}
-}  // namespace
 
 extern "C" RTW_API int rtw_accum_export_state_clamp(rtw_accum* a, float* host_sums, float* host_squares, uint32_t* host_stop,
                                                     uint32_t* host_kept, uint32_t* host_clamped, float* host_lost) {
     if (!a || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
-    const int rc = clamp_pointers(a, host_squares, host_stop, host_kept, host_clamped, host_lost);
-    return rc != RTW_OK ? rc : accum_export(a, host_sums, host_squares, host_stop, host_kept, host_clamped, host_lost);
+    const HostArrays host(host_sums, host_squares, host_stop, host_kept, host_clamped, host_lost);
+    const int rc = state_pointers(a, host, true);
+    return rc != RTW_OK ? rc : accum_export(a, host);
 }
 
 extern "C" RTW_API int rtw_accum_import_state_clamp(rtw_accum* a, const rtw_accum_info* info, const float* host_sums,
@@ -6478,8 +6401,9 @@ extern "C" RTW_API int rtw_accum_import_state_clamp(rtw_accum* a, const rtw_accu
                                                     const float* host_lost) {
     if (!a || !info || !host_sums) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
-    const int rc = clamp_pointers(a, host_squares, host_stop, host_kept, host_clamped, host_lost);
-    return rc != RTW_OK ? rc : accum_import(a, info, host_sums, host_squares, host_stop, host_kept, host_clamped, host_lost);
+    const HostArrays host(host_sums, host_squares, host_stop, host_kept, host_clamped, host_lost);
+    const int rc = state_pointers(a, host, true);
+    return rc != RTW_OK ? rc : accum_import(a, info, host);
 }
 
 extern "C" RTW_API int rtw_accum_resolve_kept(rtw_accum* a, uint32_t* d_out, void* stream) {
@@ -6497,10 +6421,10 @@ extern "C" RTW_API int rtw_accum_resolve_clamp_loss(rtw_accum* a, float* d_out, 
 extern "C" RTW_API int rtw_accum_tile_stops(rtw_accum* a, uint32_t* host_stop) {
     if (!a || !host_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
-    if (!a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
+    if (!a->st.d[ACC_STOP]) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
     HIP_TRY(hipSetDevice(a->g->device));
     if (a->g->done_recorded) HIP_TRY(hipEventSynchronize(a->g->done));
-    if (a->tiles > 0) HIP_TRY(hipMemcpy(host_stop, a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (a->tiles > 0) HIP_TRY(hipMemcpy(host_stop, a->st.d[ACC_STOP], a->bytes(ACC_STOP), hipMemcpyDeviceToHost));
     return RTW_OK;
 }
 
@@ -6512,7 +6436,8 @@ extern "C" RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_
                                        int64_t* active_pixels) {
     if (!a || !active_tiles || !active_pixels) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null argument");
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator's world was released");
-    if (!a->tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
+    uint32_t* tile_stop = a->st.get<ACC_STOP>();
+    if (!tile_stop) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)");
     if (a->info.samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the stop test needs samples >= 2");
     if (min_samples < 2) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "min_samples must be >= 2");
     hipStream_t stream = (hipStream_t)stream_;
@@ -6525,18 +6450,18 @@ extern "C" RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_
     int rc = accum_enter(a, stream);
     if (rc != RTW_OK) return rc;
     const uint32_t waves = RTW_ADAPT_BLOCK / 64;
-    if (a->kept)
-        hipLaunchKernelGGL(adapt_tiles_finite_kernel, dim3((a->tiles + waves - 1) / waves), dim3(RTW_ADAPT_BLOCK), 0, stream,
-                           (const float*)a->sums, (const float*)a->squares, (const uint32_t*)a->kept, G, a->info.samples,
-                           target, min_samples, a->tile_stop);
+    const dim3 grid((a->tiles + waves - 1) / waves), block(RTW_ADAPT_BLOCK);
+    const float *sums = a->st.get<ACC_SUMS>(), *squares = a->st.get<ACC_SQUARES>();
+    if (const uint32_t* kept = a->st.get<ACC_KEPT>())
+        hipLaunchKernelGGL(adapt_tiles_finite_kernel, grid, block, 0, stream, sums, squares, kept, G, a->info.samples, target,
+                           min_samples, tile_stop);
     else
-        hipLaunchKernelGGL(adapt_tiles_kernel, dim3((a->tiles + waves - 1) / waves), dim3(RTW_ADAPT_BLOCK), 0, stream,
-                           (const float*)a->sums, (const float*)a->squares, G, a->info.samples, target, min_samples,
-                           a->tile_stop);
+        hipLaunchKernelGGL(adapt_tiles_kernel, grid, block, 0, stream, sums, squares, G, a->info.samples, target, min_samples,
+                           tile_stop);
     HIP_TRY(hipGetLastError());
     rc = accum_leave(a, stream);
     if (rc != RTW_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(a->h_stop.data(), a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(a->h_stop.data(), tile_stop, a->bytes(ACC_STOP), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     uint32_t active = 0;
     int64_t pixels = 0;
@@ -6553,12 +6478,12 @@ extern "C" RTW_API int rtw_accum_adapt(rtw_accum* a, float target, uint32_t min_
 
 // ---- partition records (rtw.h; include/rtw_parts.h).  The kernels are rtw_parts.hip's. ----
 namespace {
-// a's device arrays in the order of its record's sections: sums, then what its flags call for
+// a's device arrays in the order of its record's sections: the table's rows its flags call for
 struct accum_sections {
     void* p[RTW_PARTS_MAX_SECTIONS];
     explicit accum_sections(const rtw_accum* a) {
         int n = 0;
-        for (void* q : {(void*)a->sums, (void*)a->squares, (void*)a->kept, (void*)a->clamped, (void*)a->lost, (void*)a->tile_stop})
+        for (void* q : a->st.d)
             if (q) p[n++] = q;
     }
 };
@@ -6621,7 +6546,7 @@ extern "C" RTW_API int rtw_accum_merge_parts(rtw_accum* whole, const void* d_gat
     rc = accum_leave(a, stream);
     if (rc != RTW_OK) return rc;
     if (flags & RTW_ACCUM_ADAPTIVE) {  // the host's copy of the stop map and its zeros, as after an adapt
-        HIP_TRY(hipMemcpyAsync(a->h_stop.data(), a->tile_stop, (size_t)a->tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(a->h_stop.data(), a->st.d[ACC_STOP], a->bytes(ACC_STOP), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         uint32_t active = 0;
         for (uint32_t t = 0; t < a->tiles; ++t) active += a->h_stop[t] == 0 ? 1u : 0u;

@@ -60,6 +60,34 @@ _U64 = ("seed", "world_fingerprint")
 _I64 = ("slots",)
 _HEADER = {**{n: np.uint32 for n in _U32}, **{n: np.int32 for n in _I32}, **{n: np.uint64 for n in _U64},
            **{n: np.int64 for n in _I64}}
+# The state arrays beside the header, in the order of the packed record's sections (rtw_device.hip's ACC_DESC is the
+# same table; a new state array is one row there and one here): the field, the flag that calls for it (0: every
+# accumulator), the dtype, the shape in terms of slots and tiles, and record_layout's key of its section.
+_ARRAYS = (("sums", 0, np.float32, ("slots", 3), "sums"),
+           ("squares", N.ACCUM_MOMENTS, np.float32, ("slots", 3), "squares"),
+           ("kept", N.ACCUM_FINITE, np.uint32, ("slots",), "kept"),
+           ("clamped", N.ACCUM_CLAMP, np.uint32, ("slots",), "clamped"),
+           ("lost", N.ACCUM_CLAMP, np.float32, ("slots", 3), "lost"),
+           ("tile_stop", N.ACCUM_ADAPTIVE, np.uint32, ("tiles",), "stop"))
+_CONVERTED = ("sums", "squares")  # taken as any array numpy converts to float32; the others must come as they are
+
+
+def _dims(shape: tuple, slots: int, tiles: int) -> tuple:
+    return tuple({"slots": int(slots), "tiles": int(tiles)}.get(d, d) for d in shape)
+
+
+def _shape_text(shape: tuple) -> str:
+    return "(" + ", ".join(map(str, shape)) + (",)" if len(shape) == 1 else ")")
+
+
+def _zeros(flags: int, slots: int, tiles: int) -> dict:
+    """A zeroed array per row of _ARRAYS that `flags` call for, None for the others."""
+    return {name: np.zeros(_dims(shape, slots, tiles), dtype) if flag == 0 or flags & flag else None
+            for name, flag, dtype, shape, _ in _ARRAYS}
+
+
+def _pointer(a: np.ndarray | None):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float if a.dtype == np.float32 else C.c_uint32))
 
 
 RECORD_VERSION = _parts.VERSION  # RTW_PARTS_VERSION
@@ -72,9 +100,8 @@ def record_layout(width: int, height: int, tile: tuple[int, int], flags: int, pa
     tw, th = tile
     per_tile = tw * th
     lay = _parts.section_offsets(-(-width // tw) * -(-height // th), part_count, per_tile,
-                                 (("sums", True, 3 * per_tile), ("squares", flags & N.ACCUM_MOMENTS, 3 * per_tile),
-                                  ("kept", flags & N.ACCUM_FINITE, per_tile), ("clamped", flags & N.ACCUM_CLAMP, per_tile),
-                                  ("lost", flags & N.ACCUM_CLAMP, 3 * per_tile), ("stop", flags & N.ACCUM_ADAPTIVE, 1)))
+                                 tuple((key, flag == 0 or flags & flag, int(np.prod(_dims(shape, per_tile, 1))))
+                                       for _, flag, _, shape, key in _ARRAYS))
     lay["per_tile"] = per_tile
     return lay
 
@@ -131,29 +158,17 @@ class AccumState:
         when the accumulator kept moments, `tile_stop` when it was adaptive, `kept` when it was finite and `clamped`
         and `lost` when it clamped (the level travels in `reserved`)."""
         arrays = {n: np.asarray(getattr(self, n), dtype=t) for n, t in _HEADER.items()}
-        arrays["sums"] = np.ascontiguousarray(self.sums, np.float32)
-        if self.squares is not None:
-            arrays["squares"] = np.ascontiguousarray(self.squares, np.float32)
-        if self.tile_stop is not None:
-            stop = np.asarray(self.tile_stop)
-            if stop.dtype != np.uint32 or stop.shape != (self.tiles,):
-                raise ValueError("tile_stop is not uint32 of shape (tiles,)")
-            arrays["tile_stop"] = np.ascontiguousarray(stop)
-        if self.kept is not None:
-            kept = np.asarray(self.kept)
-            if kept.dtype != np.uint32 or kept.shape != (int(self.slots),):
-                raise ValueError("kept is not uint32 of shape (slots,)")
-            arrays["kept"] = np.ascontiguousarray(kept)
         if (self.clamped is None) != (self.lost is None):
             raise ValueError("clamped and lost go together")
-        if self.clamped is not None:
-            clamped, lost = np.asarray(self.clamped), np.asarray(self.lost)
-            if clamped.dtype != np.uint32 or clamped.shape != (int(self.slots),):
-                raise ValueError("clamped is not uint32 of shape (slots,)")
-            if lost.dtype != np.float32 or lost.shape != (int(self.slots), 3):
-                raise ValueError("lost is not float32 of shape (slots, 3)")
-            arrays["clamped"] = np.ascontiguousarray(clamped)
-            arrays["lost"] = np.ascontiguousarray(lost)
+        for name, _, dtype, shape, _ in _ARRAYS:
+            a = getattr(self, name)
+            if a is None:
+                continue
+            if name not in _CONVERTED:
+                a = np.asarray(a)
+                if a.dtype != dtype or a.shape != _dims(shape, self.slots, self.tiles):
+                    raise ValueError(f"{name} is not {np.dtype(dtype).name} of shape {_shape_text(shape)}")
+            arrays[name] = np.ascontiguousarray(a, dtype)
         with open(path, "wb") as f:
             np.savez(f, **arrays)
 
@@ -163,7 +178,7 @@ class AccumState:
         arrays `save` writes is refused."""
         with np.load(path, allow_pickle=False) as z:
             names = set(z.files)
-            known = set(_HEADER) | {"sums", "squares", "tile_stop", "kept", "clamped", "lost"}
+            known = set(_HEADER) | {row[0] for row in _ARRAYS}
             if names - known:
                 raise ValueError(f"not an accumulator checkpoint: unexpected entries {sorted(names - known)}")
             missing = (set(_HEADER) | {"sums"}) - names
@@ -176,32 +191,17 @@ class AccumState:
                     raise ValueError(f"accumulator checkpoint: bad header field {n}")
                 vals[n] = int(a)
             arrays = {}
-            for n in ("sums", "squares", "lost"):
+            tiles = vals["slots"] // max(1, vals["tile_width"] * vals["tile_height"])
+            for n, _, dtype, shape, _ in _ARRAYS:
                 if n not in names:
                     continue
                 a = z[n]
-                if a.dtype != np.float32 or a.shape != (vals["slots"], 3):
-                    raise ValueError(f"accumulator checkpoint: {n} is not float32 of shape (slots, 3)")
+                if a.dtype != dtype or a.shape != _dims(shape, vals["slots"], tiles):
+                    raise ValueError(f"accumulator checkpoint: {n} is not {np.dtype(dtype).name} of shape {_shape_text(shape)}")
                 arrays[n] = a
-            if "tile_stop" in names:
-                a = z["tile_stop"]
-                if a.dtype != np.uint32 or a.shape != (vals["slots"] // max(1, vals["tile_width"] * vals["tile_height"]),):
-                    raise ValueError("accumulator checkpoint: tile_stop is not uint32 of shape (tiles,)")
-                arrays["tile_stop"] = a
-            if "kept" in names:
-                a = z["kept"]
-                if a.dtype != np.uint32 or a.shape != (vals["slots"],):
-                    raise ValueError("accumulator checkpoint: kept is not uint32 of shape (slots,)")
-                arrays["kept"] = a
-            if "clamped" in names:
-                a = z["clamped"]
-                if a.dtype != np.uint32 or a.shape != (vals["slots"],):
-                    raise ValueError("accumulator checkpoint: clamped is not uint32 of shape (slots,)")
-                arrays["clamped"] = a
             if ("clamped" in names) != ("lost" in names):
                 raise ValueError("accumulator checkpoint: clamped and lost go together")
-        return cls(**vals, sums=arrays["sums"], squares=arrays.get("squares"), tile_stop=arrays.get("tile_stop"),
-                   kept=arrays.get("kept"), clamped=arrays.get("clamped"), lost=arrays.get("lost"))
+        return cls(**vals, **arrays)
 
     def _frame_tiles(self) -> int:
         return -(-int(self.width) // int(self.tile_width)) * -(-int(self.height) // int(self.tile_height))
@@ -225,12 +225,7 @@ class AccumState:
         adaptive = bool(flags & N.ACCUM_ADAPTIVE)
         per_tile, n_tiles = int(first.tile_width) * int(first.tile_height), first._frame_tiles()
         slots = n_tiles * per_tile
-        sums = np.zeros((slots, 3), np.float32)
-        squares = np.zeros((slots, 3), np.float32) if flags & N.ACCUM_MOMENTS else None
-        kept = np.zeros(slots, np.uint32) if flags & N.ACCUM_FINITE else None
-        clamped = np.zeros(slots, np.uint32) if flags & N.ACCUM_CLAMP else None
-        lost = np.zeros((slots, 3), np.float32) if flags & N.ACCUM_CLAMP else None
-        stop = np.zeros(n_tiles, np.uint32) if adaptive else None
+        whole = _zeros(flags, slots, n_tiles)
         samples = int(first.samples)
         for r in range(count):
             s = by_part[r]
@@ -240,10 +235,8 @@ class AccumState:
             if not adaptive and int(s.samples) != samples:
                 raise ValueError(f"part {r}: samples differs (only adaptive parts may differ)")
             samples = max(samples, int(s.samples))
-            for name, dst, shape in (("sums", sums, (at.size, 3)), ("squares", squares, (at.size, 3)), ("kept", kept, (at.size,)),
-                                     ("clamped", clamped, (at.size,)), ("lost", lost, (at.size, 3)),
-                                     ("tile_stop", stop, (tiles.size,))):
-                src = getattr(s, name)
+            for name, _, _, shape, _ in _ARRAYS:
+                src, dst, shape = getattr(s, name), whole[name], _dims(shape, at.size, tiles.size)
                 if (src is None) != (dst is None):
                     raise ValueError(f"part {r}: {name} does not go with the flags")
                 if dst is None:
@@ -259,7 +252,7 @@ class AccumState:
                     raise ValueError(f"part {r}: tile_stop[{int(np.flatnonzero(bad)[0])}] is 1 or above the part's samples")
         head = first.header()
         head.update(part_index=0, part_count=1, samples=samples, slots=slots)
-        return cls(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept, clamped=clamped, lost=lost)
+        return cls(**head, **whole)
 
     def split(self, part_count: int) -> list["AccumState"]:
         """The inverse of `merge`: the states of parts (0..part_count-1, part_count) of this whole-image state.  A
@@ -280,17 +273,17 @@ class AccumState:
         out = []
         for r in range(part_count):
             tiles, at = _parts.part_tiles(n_tiles, (r, part_count)), _parts.part_slots(n_tiles, per_tile, (r, part_count))
-            stop = None if self.tile_stop is None else np.ascontiguousarray(self.tile_stop[tiles])
+            part = {}
+            for name, _, _, shape, _ in _ARRAYS:
+                a = getattr(self, name)
+                part[name] = None if a is None else np.ascontiguousarray(a[tiles if shape[0] == "tiles" else at])
+            stop = part["tile_stop"]
             samples = int(self.samples)
             if stop is not None and not (stop == 0).any():
                 samples = int(stop.max()) if stop.size else 0
             head = self.header()
             head.update(part_index=r, part_count=part_count, samples=samples, slots=int(at.size))
-            out.append(AccumState(**head, sums=np.ascontiguousarray(self.sums[at]),
-                                  squares=None if self.squares is None else np.ascontiguousarray(self.squares[at]),
-                                  tile_stop=stop, kept=None if self.kept is None else np.ascontiguousarray(self.kept[at]),
-                                  clamped=None if self.clamped is None else np.ascontiguousarray(self.clamped[at]),
-                                  lost=None if self.lost is None else np.ascontiguousarray(self.lost[at])))
+            out.append(AccumState(**head, **part))
         return out
 
     def packed(self, stride_bytes: int | None = None) -> np.ndarray:
@@ -298,8 +291,7 @@ class AccumState:
         with zeros to `stride_bytes`: what a rank without device-aware collectives sends."""
         count = max(1, int(self.part_count))
         lay = record_layout(int(self.width), int(self.height), (int(self.tile_width), int(self.tile_height)), int(self.flags), count)
-        sections = (("sums", self.sums), ("squares", self.squares), ("kept", self.kept), ("clamped", self.clamped),
-                    ("lost", self.lost), ("stop", self.tile_stop))
+        sections = tuple((key, getattr(self, name)) for name, _, _, _, key in _ARRAYS)
         for name, arr in sections:
             if (arr is None) != (lay[name] is None):
                 raise ValueError(f"{name} does not go with the flags")
@@ -309,14 +301,6 @@ class AccumState:
 
 
 assert [f.name for f in fields(AccumState)][:len(_HEADER)] == [n for n, _ in N.AccumInfo._fields_]
-
-
-def _f32p(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _u32p(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
 class Accumulator:
@@ -531,32 +515,23 @@ class Accumulator:
     def tile_stops(self) -> np.ndarray:
         """The stop map: per local tile 0 (active) or the sample count it stopped at (uint32, shape (tiles,))."""
         stop = np.zeros(self.tiles, np.uint32)
-        check(lib().rtw_accum_tile_stops(self._h, _u32p(stop)))
+        check(lib().rtw_accum_tile_stops(self._h, _pointer(stop)))
         return stop
 
     def state(self) -> AccumState:
         i = self.info()
-        sums = np.zeros((i.slots, 3), np.float32)
-        squares = np.zeros((i.slots, 3), np.float32) if self.moments else None
-        stop = kept = clamped = lost = None
+        arrays = _zeros(int(i.flags), i.slots, self.tiles)
+        p = {name: _pointer(a) for name, a in arrays.items()}
         if self.clamp is not None:
-            stop = np.zeros(self.tiles, np.uint32) if self.adaptive else None
-            kept, clamped, lost = np.zeros(i.slots, np.uint32), np.zeros(i.slots, np.uint32), np.zeros((i.slots, 3), np.float32)
-            check(lib().rtw_accum_export_state_clamp(self._h, _f32p(sums), _f32p(squares) if squares is not None else None,
-                                                     _u32p(stop) if stop is not None else None, _u32p(kept), _u32p(clamped),
-                                                     _f32p(lost)))
+            check(lib().rtw_accum_export_state_clamp(self._h, p["sums"], p["squares"], p["tile_stop"], p["kept"], p["clamped"],
+                                                     p["lost"]))
         elif self.finite:  # the one pair for every flag combination
-            stop = np.zeros(self.tiles, np.uint32) if self.adaptive else None
-            kept = np.zeros(i.slots, np.uint32)
-            check(lib().rtw_accum_export_state(self._h, _f32p(sums), _f32p(squares) if squares is not None else None,
-                                               _u32p(stop) if stop is not None else None, _u32p(kept)))
+            check(lib().rtw_accum_export_state(self._h, p["sums"], p["squares"], p["tile_stop"], p["kept"]))
         elif self.adaptive:
-            stop = np.zeros(self.tiles, np.uint32)
-            check(lib().rtw_accum_export_adaptive(self._h, _f32p(sums), _f32p(squares), _u32p(stop)))
+            check(lib().rtw_accum_export_adaptive(self._h, p["sums"], p["squares"], p["tile_stop"]))
         else:
-            check(lib().rtw_accum_export(self._h, _f32p(sums), _f32p(squares) if squares is not None else None))
-        return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, sums=sums, squares=squares, tile_stop=stop,
-                          kept=kept, clamped=clamped, lost=lost)
+            check(lib().rtw_accum_export(self._h, p["sums"], p["squares"]))
+        return AccumState(**{n: int(getattr(i, n)) for n in _HEADER}, **arrays)
 
     def packed_bytes(self) -> int:
         """The bytes of this accumulator's packed record (the same for every part of its part_count)."""
@@ -588,39 +563,31 @@ class Accumulator:
         i = N.AccumInfo()
         for n in _HEADER:
             setattr(i, n, getattr(state, n))
-        sums = np.ascontiguousarray(state.sums, np.float32)
-        squares = None if state.squares is None else np.ascontiguousarray(state.squares, np.float32)
-        if sums.size != 3 * state.slots or (squares is not None and squares.size != sums.size):
-            raise ValueError("state arrays do not hold 3 * slots floats")
-        sq = _f32p(squares) if squares is not None else None
-        if self.clamp is not None or state.clamped is not None or state.lost is not None:
-            # the clamp pair: it refuses what the flags do not call for, and another level by name
-            arr = {}
-            for n, t, shape in (("tile_stop", np.uint32, (self.tiles,)), ("kept", np.uint32, (state.slots,)),
-                                ("clamped", np.uint32, (state.slots,)), ("lost", np.float32, (state.slots, 3))):
-                v = getattr(state, n)
-                arr[n] = None if v is None else np.ascontiguousarray(v, t)
-                if arr[n] is not None and arr[n].shape != shape:
-                    raise ValueError(f"state.{n} does not have shape {shape}")
-            ptr = {n: None if v is None else (_f32p(v) if n == "lost" else _u32p(v)) for n, v in arr.items()}
-            check(lib().rtw_accum_import_state_clamp(self._h, C.byref(i), _f32p(sums), sq, ptr["tile_stop"], ptr["kept"],
-                                                     ptr["clamped"], ptr["lost"]))
+        # the clamp pair refuses what the flags do not call for, and another level by name
+        clamp_pair = self.clamp is not None or state.clamped is not None or state.lost is not None
+        arr = {}
+        for name, _, dtype, shape, _ in _ARRAYS:
+            a = getattr(state, name)
+            arr[name] = None if a is None else np.ascontiguousarray(a, dtype)
+            if arr[name] is None:
+                continue
+            if name in _CONVERTED:
+                if arr[name].size != 3 * state.slots:
+                    raise ValueError("state arrays do not hold 3 * slots floats")
+            elif arr[name].shape != _dims(shape, state.slots, self.tiles):
+                if clamp_pair:
+                    raise ValueError(f"state.{name} does not have shape {_dims(shape, state.slots, self.tiles)}")
+                raise ValueError(f"state.{name} does not hold one entry per {'tile' if shape[0] == 'tiles' else 'slot'}")
+        p = {name: _pointer(a) for name, a in arr.items()}
+        if clamp_pair:
+            check(lib().rtw_accum_import_state_clamp(self._h, C.byref(i), p["sums"], p["squares"], p["tile_stop"], p["kept"],
+                                                     p["clamped"], p["lost"]))
         elif self.finite or state.kept is not None:  # the one pair: it refuses what the flags do not call for
-            stop = None if state.tile_stop is None else np.ascontiguousarray(state.tile_stop, np.uint32)
-            kept = None if state.kept is None else np.ascontiguousarray(state.kept, np.uint32)
-            if stop is not None and stop.shape != (self.tiles,):
-                raise ValueError("state.tile_stop does not hold one entry per tile")
-            if kept is not None and kept.shape != (state.slots,):
-                raise ValueError("state.kept does not hold one entry per slot")
-            check(lib().rtw_accum_import_state(self._h, C.byref(i), _f32p(sums), sq, _u32p(stop) if stop is not None else None,
-                                               _u32p(kept) if kept is not None else None))
+            check(lib().rtw_accum_import_state(self._h, C.byref(i), p["sums"], p["squares"], p["tile_stop"], p["kept"]))
         elif state.tile_stop is not None:
-            stop = np.ascontiguousarray(state.tile_stop, np.uint32)
-            if stop.shape != (self.tiles,):
-                raise ValueError("state.tile_stop does not hold one entry per tile")
-            check(lib().rtw_accum_import_adaptive(self._h, C.byref(i), _f32p(sums), sq, _u32p(stop)))
+            check(lib().rtw_accum_import_adaptive(self._h, C.byref(i), p["sums"], p["squares"], p["tile_stop"]))
         else:  # (refused by an adaptive accumulator: its state includes the stop map)
-            check(lib().rtw_accum_import(self._h, C.byref(i), _f32p(sums), sq))
+            check(lib().rtw_accum_import(self._h, C.byref(i), p["sums"], p["squares"]))
 
 
 def merge_parts_host(like: AccumState, gathered: np.ndarray, stride_bytes: int, part_count: int) -> AccumState:
@@ -637,27 +604,19 @@ def merge_parts_host(like: AccumState, gathered: np.ndarray, stride_bytes: int, 
     need = max(0, part_count - 1) * stride_bytes + N.packed_bytes(p, flags, max(1, part_count))
     if stride_bytes > 0 and buf.size < need:
         raise ValueError(f"the gathered array holds fewer than the {need} bytes of {part_count} records")
-    sums = np.zeros((slots, 3), np.float32)
-    squares = np.zeros((slots, 3), np.float32) if flags & N.ACCUM_MOMENTS else None
-    kept = np.zeros(slots, np.uint32) if flags & N.ACCUM_FINITE else None
-    stop = np.zeros(n_tiles, np.uint32) if flags & N.ACCUM_ADAPTIVE else None
+    arrays = _zeros(flags, slots, n_tiles)
+    ptr = [_pointer(arrays[name]) for name, *_ in _ARRAYS]  # (the C calls take them in the record's order)
     samples = C.c_uint32()
     if flags & N.ACCUM_CLAMP:  # (records of another level than `like`'s are refused naming clamp)
-        clamped, lost = np.zeros(slots, np.uint32), np.zeros((slots, 3), np.float32)
         check(lib().rtw_accum_merge_parts_host_clamp(C.byref(p), flags, like.clamp, C.c_void_p(buf.ctypes.data), stride_bytes,
-                                                     part_count, _f32p(sums), _f32p(squares) if squares is not None else None,
-                                                     _u32p(kept) if kept is not None else None, _u32p(clamped), _f32p(lost),
-                                                     _u32p(stop) if stop is not None else None, C.byref(samples)))
-        head = like.header()
-        head.update(part_index=0, part_count=1, samples=int(samples.value), slots=slots)
-        return AccumState(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept, clamped=clamped, lost=lost)
-    check(lib().rtw_accum_merge_parts_host(C.byref(p), flags, C.c_void_p(buf.ctypes.data), stride_bytes, part_count,
-                                           _f32p(sums), _f32p(squares) if squares is not None else None,
-                                           _u32p(kept) if kept is not None else None,
-                                           _u32p(stop) if stop is not None else None, C.byref(samples)))
+                                                     part_count, *ptr, C.byref(samples)))
+    else:
+        sums, squares, kept, _, _, stop = ptr
+        check(lib().rtw_accum_merge_parts_host(C.byref(p), flags, C.c_void_p(buf.ctypes.data), stride_bytes, part_count,
+                                               sums, squares, kept, stop, C.byref(samples)))
     head = like.header()
     head.update(part_index=0, part_count=1, samples=int(samples.value), slots=slots)
-    return AccumState(**head, sums=sums, squares=squares, tile_stop=stop, kept=kept)
+    return AccumState(**head, **arrays)
 
 
 def world_fingerprint(world: World) -> int:

@@ -373,3 +373,162 @@ def test_two_ranks_on_one_gpu(worlds, tmp_path):
             pytest.fail("the two ranks did not finish in 120 s")
     same_state(AccumState.load(tmp_path / "whole.npz"), want, "the two ranks' merged state")
     assert_bit_identical(np.load(tmp_path / "loss.npy"), want_loss, "the two ranks' loss")
+
+
+# ---- 8. the flag sets no other test resumes: export -> import -> continue, every array and resolve -------------------
+# Which test file drives add / the resolves / noise / adapt / export-import-continue for each of the nine legal flag
+# sets (P test_gpu_progressive, A _adaptive, F _finite, C this file, R _parts; - does not apply):
+#   none P P - - P    M   P P P - R    F    F F - - gap    MF   F F F - F    FC C C - - gap
+#   MFC  C C C - C    MA  A A A A A    MFA  F F F F gap    MFCA C C gap C gap
+# This test fills the gaps.  suzanne at L = 0.5 clamps and rejects, as in test 2.
+FLAG_SETS = {"F": dict(finite=True), "FC": dict(clamp=0.5), "MFA": dict(adaptive=True, finite=True),
+             "MFCA": dict(adaptive=True, clamp=0.5)}
+
+
+@pytest.fixture
+def suzanne_on_device(worlds):
+    dw = R.DeviceWorld(worlds("suzanne"), 0)
+    yield dw
+    dw.release()
+
+
+@pytest.mark.parametrize("part,layout", [((0, 1), N.LAYOUT_IMAGE), ((1, 3), N.LAYOUT_TILES)], ids=["whole", "part1of3_tiles"])
+@pytest.mark.parametrize("flag_set", list(FLAG_SETS))
+def test_every_flag_set_resumes_bit_for_bit(worlds, suzanne_on_device, flag_set, part, layout):
+    world, size, level = worlds("suzanne"), R.Size2i(20, 12), 0.5  # 3 x 2 tiles of 8 x 8, padded in both axes
+    moments, clamp, adaptive = "M" in flag_set, "C" in flag_set, "A" in flag_set
+    slots = tile_slots(size, TILE, part)
+    owned, per_tile = slots >= 0, TILE[0] * TILE[1]
+    assert 0 < owned.sum() < owned.size
+    colors = F.to_slots(F.oracle_samples(world, R.render_params(size, 5, DEPTH, seed=SEED), 5), slots)
+
+    def restated(n):  # (sums, squares, kept, clamped, lost) after n samples
+        if clamp:
+            return K.accumulate(colors[:n], f32(level), moments=moments)
+        return F.accumulate(colors[:n], moments=moments) + (None, None)
+
+    names = ("sums", "squares", "kept", "clamped", "lost")
+    ref = {n: restated(n) for n in (3, 5)}
+    stop, target = np.zeros(owned.size // per_tile, np.uint32), None
+    if adaptive:  # the median tile E at 3 samples: some tiles stop there, some go on
+        E = F.tiles_E(*ref[3][:3], size, TILE, part)
+        target = float(f32(np.median(E)))
+        stop = A.stop_rule(stop, E, 3, target, 2)
+        print("target", target, "E", E, "stop", stop)
+        assert (stop == 3).any() and (stop == 0).any()
+    dw = suzanne_on_device
+    accs = [R.Accumulator(dw, size, DEPTH, seed=SEED, tile=TILE, part=part, layout=layout, **FLAG_SETS[flag_set]) for _ in range(3)]
+    straight, first, resumed = accs
+    for acc in (straight, first):
+        acc.add(3)
+        if adaptive:
+            assert acc.adapt(target, 2)[0] == int((stop == 0).sum()) and (acc.tile_stops() == stop).all()
+    straight.add(2)
+    saved = first.state()
+    resumed.load_state(saved)
+    same_state(resumed.state(), saved, "loaded")
+    resumed.add(2)
+    got, want = resumed.state(), straight.state()
+    same_state(got, want, "resumed against 5 samples added straight")
+    assert got.samples == 5 and got.flags == (1 if moments else 0) + (2 if adaptive else 0) + 4 + (8 if clamp else 0)
+    # the state arrays against the restatement: every tile at its own count
+    slot_n = A.expand(np.where(stop != 0, stop, 5), per_tile)
+    for n in np.unique(slot_n):
+        sel = slot_n == n
+        for name, arr in zip(names, ref[int(n)]):
+            have = getattr(got, name)
+            assert (have is None) == (arr is None), name
+            if arr is not None:
+                assert (have.view(np.uint32)[sel] == arr.view(np.uint32)[sel]).all(), (name, int(n))
+    assert (got.tile_stop is None) is (not adaptive) and (not adaptive or (got.tile_stop == stop).all())
+    print("rejected", int((slot_n[owned] - got.kept[owned]).sum()), "clamped", int(got.clamped.sum()) if clamp else None)
+    if clamp:
+        assert (got.clamped > 0).any()
+    # every resolve, bit for bit
+    resolves = ["image", "sample_counts", "kept_counts"] + (["stderr"] if moments else []) + (["clamped_counts", "clamp_loss"] if clamp else [])
+    for name in resolves:
+        a, b = getattr(resumed, name)(), getattr(straight, name)()
+        assert a.shape == b.shape and (a.view(np.uint32) == b.view(np.uint32)).all(), name
+    assert (by_slot(resumed.sample_counts(), slots, layout)[:, 0] == slot_n[owned]).all()
+    assert (by_slot(resumed.kept_counts(), slots, layout)[:, 0] == got.kept[owned]).all()
+    assert_bit_identical(by_slot(resumed.image(), slots, layout), F.mean(got.sums, got.kept)[owned], "image")
+    if moments:
+        assert resumed.noise() == straight.noise()
+        want_noise, pixels = F.noise(F.stats(got.sums, got.squares, got.kept)[1], owned)
+        noise, counted = resumed.noise()
+        print(f"noise {noise!r} numpy {want_noise!r} pixels {counted} of {int(owned.sum())}")
+        assert counted == pixels and abs(noise - want_noise) <= 1e-9 * abs(want_noise)
+    if adaptive:  # the stop test after an import decides as the straight accumulator's
+        assert resumed.adapt(target, 2) == straight.adapt(target, 2)
+        assert (resumed.tile_stops() == straight.tile_stops()).all()
+
+
+# ---- 9. the export / import pairs' refusals, word for word ----------------------------------------------------------
+FINITE_TEXT = ": the accumulator has RTW_ACCUM_FINITE, whose state includes kept: use rtw_accum_export_state / rtw_accum_import_state"
+CLAMP_TEXT = (": the accumulator has RTW_ACCUM_CLAMP, whose state includes clamped and lost: use rtw_accum_export_state_clamp / "
+              "rtw_accum_import_state_clamp")
+NO_CLAMP_TEXT = "the accumulator has no RTW_ACCUM_CLAMP: use rtw_accum_export_state / rtw_accum_import_state"
+# (accumulator, call, arguments: s sums, q squares, t tile_stop, k kept, c clamped, l lost, - null; the text)
+REFUSAL_TEXTS = [
+    ("fin", "export", "sq", "rtw_accum_export" + FINITE_TEXT),
+    ("fin", "import", "sq", "rtw_accum_import" + FINITE_TEXT),
+    ("fin", "export_adaptive", "sqt", "rtw_accum_export_adaptive" + FINITE_TEXT),
+    ("fin", "import_adaptive", "sqt", "rtw_accum_import_adaptive" + FINITE_TEXT),
+    ("cl", "export", "sq", "rtw_accum_export" + CLAMP_TEXT),  # (the clamp's refusal comes before the finite one)
+    ("cl", "import", "sq", "rtw_accum_import" + CLAMP_TEXT),
+    ("cl", "export_adaptive", "sqt", "rtw_accum_export_adaptive" + CLAMP_TEXT),
+    ("cl", "import_adaptive", "sqt", "rtw_accum_import_adaptive" + CLAMP_TEXT),
+    ("cl", "export_state", "sq-k", "rtw_accum_export_state" + CLAMP_TEXT),
+    ("cl", "import_state", "sq-k", "rtw_accum_import_state" + CLAMP_TEXT),
+    ("plain", "export", "s-", "null squares (the accumulator keeps moments)"),
+    ("plain", "import", "s-", "null squares (the accumulator keeps moments)"),
+    ("plain", "export_adaptive", "sqt", "the accumulator is not adaptive (RTW_ACCUM_ADAPTIVE)"),
+    ("plain", "import_adaptive", "sqt", "tile_stop given, but the accumulator is not adaptive"),
+    ("ad", "import", "sq", "an adaptive accumulator's state includes tile_stop: import it with rtw_accum_import_adaptive"),
+    ("ad", "export_adaptive", "sq-", "null argument"),
+    # the state pair: squares, then tile_stop, then kept, whichever comes first
+    ("fin", "export_state", "s-t-", "null squares (the accumulator has RTW_ACCUM_MOMENTS)"),
+    ("fin", "export_state", "sqt-", "tile_stop given, but the accumulator has no RTW_ACCUM_ADAPTIVE"),
+    ("fin", "import_state", "sq--", "null kept (the accumulator has RTW_ACCUM_FINITE)"),
+    ("plain", "import_state", "sq-k", "kept given, but the accumulator has no RTW_ACCUM_FINITE"),
+    ("ad", "export_state", "sq--", "null tile_stop (the accumulator has RTW_ACCUM_ADAPTIVE)"),
+    ("alone", "export_state", "sq-k", "squares given, but the accumulator has no RTW_ACCUM_MOMENTS"),
+    # the clamp pair: the flag, then the state pair's rule, then clamped, then lost
+    ("fin", "export_state_clamp", "s-----", NO_CLAMP_TEXT),
+    ("fin", "import_state_clamp", "sq-kcl", NO_CLAMP_TEXT),
+    ("cl", "export_state_clamp", "s--k--", "null squares (the accumulator has RTW_ACCUM_MOMENTS)"),
+    ("cl", "import_state_clamp", "sqtk--", "tile_stop given, but the accumulator has no RTW_ACCUM_ADAPTIVE"),
+    ("cl", "export_state_clamp", "sq----", "null kept (the accumulator has RTW_ACCUM_FINITE)"),
+    ("cl", "export_state_clamp", "sq-k--", "null clamped (the accumulator has RTW_ACCUM_CLAMP)"),
+    ("cl", "import_state_clamp", "sq-kc-", "null lost (the accumulator has RTW_ACCUM_CLAMP)"),
+    ("cl", "export_state_clamp", "-q-kcl", "null argument"),
+]
+
+
+@pytest.fixture(scope="module")
+def refusing(worlds):
+    size = R.Size2i(20, 12)
+    dw = R.DeviceWorld(worlds("simple_plane"), 0)
+    accs = {"plain": R.Accumulator(dw, size, DEPTH, seed=SEED, moments=True),
+            "ad": R.Accumulator(dw, size, DEPTH, seed=SEED, adaptive=True),
+            "alone": R.Accumulator(dw, size, DEPTH, seed=SEED, finite=True),
+            "fin": R.Accumulator(dw, size, DEPTH, seed=SEED, moments=True, finite=True),
+            "cl": R.Accumulator(dw, size, DEPTH, seed=SEED, moments=True, clamp=0.25)}
+    for acc in accs.values():
+        acc.add(2)
+    yield accs
+    dw.release()
+
+
+@pytest.mark.parametrize("who,call,args,text", REFUSAL_TEXTS, ids=[f"{w}-{c}-{a}" for w, c, a, _ in REFUSAL_TEXTS])
+def test_refusal_texts(refusing, who, call, args, text):
+    acc, L = refusing[who], N.lib()
+    before = acc.state()
+    slots, tiles = acc.slots, acc.tiles
+    arrays = {"s": np.zeros((slots, 3), f32), "q": np.zeros((slots, 3), f32), "t": np.zeros(tiles, np.uint32),
+              "k": np.zeros(slots, np.uint32), "c": np.zeros(slots, np.uint32), "l": np.zeros((slots, 3), f32)}
+    ptrs = [None if a == "-" else arrays[a].ctypes.data_as(f32p if a in "sql" else u32p) for a in args]
+    head = [C.byref(acc.info())] if call.startswith("import") else []
+    assert getattr(L, "rtw_accum_" + call)(acc._h, *head, *ptrs) == N.RTW_ERR_INVALID_ARGUMENT
+    assert L.rtw_last_error().decode() == text
+    same_state(acc.state(), before, "a refused call changes nothing")
