@@ -86,8 +86,10 @@ def uniform_new(low, high):
     return low, scale
 
 
-def primary_hit(world, size, seed, x, y, s):
-    """The oracle's first hit of sample `s` of pixel (x, y): an OracleHit (hit == 0: a miss)."""
+def primary_ray(world, size, seed, x, y, s):
+    """The oracle's camera ray of sample `s` of pixel (x, y): the (seed, pixel, sample) stream, the jitter,
+    rtw_oracle_camera_ray.  Returns (origin, direction, time, state, (px, py)): ctypes f32 values, the stream
+    carried on, the jittered point."""
     W, H = size.width, size.height
     L = O.lib()
     (lx, sx), (ly, sy) = uniform_new(0, f32(1) / f32(W - 1)), uniform_new(0, f32(1) / f32(H - 1))
@@ -99,8 +101,14 @@ def primary_hit(world, size, seed, x, y, s):
     state = (C.c_uint64 * 2)(rng.s0, rng.s1)
     o, d, t = (C.c_float * 3)(), (C.c_float * 3)(), C.c_float()
     assert L.rtw_oracle_camera_ray(C.byref(world.raw.camera), px, py, state, o, d, C.byref(t)) == 0
+    return o, d, t, state, (px, py)
+
+
+def primary_hit(world, size, seed, x, y, s):
+    """The oracle's first hit of sample `s` of pixel (x, y): an OracleHit (hit == 0: a miss)."""
+    o, d, t, state, _ = primary_ray(world, size, seed, x, y, s)
     h = O.OracleHit()
-    assert L.rtw_oracle_scene_hit(world.ptr(), o, d, t, f32(0.001), f32(np.inf), state, C.byref(h)) == 0
+    assert O.lib().rtw_oracle_scene_hit(world.ptr(), o, d, t, f32(0.001), f32(np.inf), state, C.byref(h)) == 0
     return h
 
 
