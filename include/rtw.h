@@ -743,6 +743,66 @@ RTW_API int rtw_aov_export_state(rtw_aov* a, float* host_albedo, float* host_nor
 RTW_API int rtw_aov_import_state(rtw_aov* a, const rtw_aov_state_info* info, const float* host_albedo,
                                  const float* host_normal, const float* host_depth, const uint32_t* host_hits);
 
+/* ---- ray queries: closest hit and occlusion for the caller's rays ---------------------------- */
+/* What a ray of the caller's hits: a pick, a visibility or shadow test, a bake, a probe of one
+ * bounce.  hits[i] is Scene::hit (hittable.rs:130-137) of ray i over [t_start, rays[i].t_end): the reference's
+ * depth-first walk of the reference tree, ties included, with its f32 arithmetic -- t, position, normal (flipped
+ * to oppose the ray, front_face telling which way), uv, front_face and material are the reference's bits.  leaf is
+ * the index into rtw_world.leaves.  The direction need not be unit length (t is in units of it); time may be any
+ * finite float: it moves Animation leaves and nothing else.  A miss gives leaf = material = -1, front_face = 0, t
+ * the ray's own t_end (its bits) and +0.0 elsewhere.  albedo[i] (RTW_CAST_ALBEDO) is the AOV pass's value at that
+ * hit: (1, 1, 1) on a miss and on a dielectric, else 0 + 1 * the material's texture at the hit.
+ * A volume leaf draws its distance from a stream of the ray's own: ray i starts from
+ * rtw_sample_stream(rtw_seed_key(seed), (uint32_t)i, stream).  A batch is reproducible, and a ray's answer depends
+ * on its index and on nothing else in the batch (in a world without volume leaves, not on its index either).
+ * out[i] of the occlusion calls is hits[i].leaf >= 0 of the closest-hit call with the same params: the same walk in
+ * the same order, left at the first leaf that accepts (until then the range's end has not moved, so its steps and
+ * draws are a prefix of the closest-hit walk's).
+ *
+ * Refused with RTW_ERR_INVALID_ARGUMENT and a message naming the field, the parameters before the world, with
+ * nothing launched or written: null params, rays, hits or out; flags with an unknown bit (the occlusion calls know
+ * none); reserved0 != 0; a t_start that is NaN or infinite; n < 0 or n > 2^31 - 1; albedo NULL with RTW_CAST_ALBEDO
+ * or non-NULL without it; device rays or hits that are not 16-byte aligned (the kernel moves a ray as two and a
+ * record as three 16-byte words); a NULL world; a world that rtw_world_release has taken (the library keeps the set
+ * of live handles for this; a handle is an address, so a stale one reads as live again once a later
+ * rtw_world_upload has been given the freed address: drop a handle when you release it).  n == 0 is RTW_OK with
+ * nothing launched or written.  The rays' own values are device data and are not validated: the walk is bounded by
+ * the tree, so a ray with NaN or infinite components returns like any other (what it returns is the f32
+ * arithmetic's answer).
+ * The calls use none of the world's scratch: they interleave freely with frames, colour accumulators and AOV
+ * accumulators of the world.  The *_device calls are asynchronous on `stream`, one launch each; rtw_cast and
+ * rtw_occluded take host arrays (any alignment), stage them and wait. */
+typedef struct rtw_ray { /* 32 bytes */
+    float origin[3];
+    float time;
+    float direction[3];
+    float t_end; /* the range's end, exclusive; +inf for none */
+} rtw_ray;
+typedef struct rtw_hit { /* 48 bytes */
+    float t;
+    int32_t leaf; /* index into rtw_world.leaves, -1 on a miss */
+    float position[3];
+    float normal[3];
+    float uv[2];
+    int32_t front_face; /* 1: the ray met the outside of the surface */
+    int32_t material;   /* index into rtw_world.materials, -1 on a miss */
+} rtw_hit;
+#define RTW_CAST_ALBEDO 1u
+typedef struct rtw_cast_params {
+    uint32_t flags;  /* RTW_CAST_* */
+    float t_start;   /* the range's start, inclusive (the renderer's is 0.001) */
+    uint64_t seed;   /* the volume leaves' streams */
+    uint32_t stream;
+    uint32_t reserved0; /* 0 */
+} rtw_cast_params;
+RTW_API int rtw_cast_device(rtw_gpu_world* gw, const rtw_cast_params* params, const rtw_ray* d_rays, int64_t n,
+                            rtw_hit* d_hits, float* d_albedo /* n * 3 floats, iff RTW_CAST_ALBEDO */, void* stream);
+RTW_API int rtw_occluded_device(rtw_gpu_world* gw, const rtw_cast_params* params, const rtw_ray* d_rays, int64_t n,
+                                uint8_t* d_out /* n bytes, 1 or 0 */, void* stream);
+RTW_API int rtw_cast(rtw_gpu_world* gw, const rtw_cast_params* params, const rtw_ray* rays, int64_t n, rtw_hit* hits,
+                     float* albedo);
+RTW_API int rtw_occluded(rtw_gpu_world* gw, const rtw_cast_params* params, const rtw_ray* rays, int64_t n, uint8_t* out);
+
 /* ---- preview denoiser ---------------------------------------------------------------------- */
 /* A variance-guided a-trous filter for accumulator previews, built on nothing but images:
  * a colour image, the standard error of its channels (rtw_accum_resolve_stderr) and an optional guide of

@@ -7,6 +7,7 @@ Camera.build()..., WorldBuilder / NodeBuilder, demo worlds, rendering.render(...
 """
 from . import image_io
 from .aov import AovAccumulator, AovState, render_aov
+from .cast import CastResult, RayCaster, cast_rays
 from .denoise import Denoiser, denoise_host
 from .progressive import (
     Accumulator,
@@ -50,17 +51,20 @@ __all__ = [
     "AssetSet",
     "BackgroundColor",
     "Camera",
+    "CastResult",
     "DEMO_WORLDS",
     "Denoiser",
     "DeviceWorld",
     "MultiDeviceWorld",
     "NodeBuilder",
     "NodeRef",
+    "RayCaster",
     "RenderMode",
     "Rng",
     "Size2i",
     "World",
     "WorldBuilder",
+    "cast_rays",
     "demo_world",
     "denoise_host",
     "device_count",

@@ -249,6 +249,35 @@ class AovStateInfo(C.Structure):  # rtw_aov_state_info: fixed-width fields, no p
     ]
 
 
+CAST_ALBEDO = 1  # RTW_CAST_*
+
+
+class Ray(C.Structure):  # rtw_ray, 32 bytes
+    _fields_ = [("origin", F3), ("time", C.c_float), ("direction", F3), ("t_end", C.c_float)]
+
+
+class Hit(C.Structure):  # rtw_hit, 48 bytes
+    _fields_ = [
+        ("t", C.c_float),
+        ("leaf", C.c_int32),
+        ("position", F3),
+        ("normal", F3),
+        ("uv", F2),
+        ("front_face", C.c_int32),
+        ("material", C.c_int32),
+    ]
+
+
+class CastParams(C.Structure):  # rtw_cast_params
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("t_start", C.c_float),
+        ("seed", C.c_uint64),
+        ("stream", C.c_uint32),
+        ("reserved0", C.c_uint32),
+    ]
+
+
 class DenoiseParams(C.Structure):  # rtw_denoise_params
     _fields_ = [
         ("width", C.c_int32),
@@ -400,6 +429,10 @@ _SIGS = {
                                        C.POINTER(C.c_uint32)]),
     "rtw_aov_import_state": (C.c_int, [_P, C.POINTER(AovStateInfo), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "rtw_cast_device": (C.c_int, [_P, C.POINTER(CastParams), _P, C.c_int64, _P, _P, _P]),
+    "rtw_occluded_device": (C.c_int, [_P, C.POINTER(CastParams), _P, C.c_int64, _P, _P]),
+    "rtw_cast": (C.c_int, [_P, C.POINTER(CastParams), _P, C.c_int64, _P, _P]),
+    "rtw_occluded": (C.c_int, [_P, C.POINTER(CastParams), _P, C.c_int64, _P]),
     "rtw_denoiser_run_albedo": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
     "rtw_denoise_host_albedo": (C.c_int, [C.POINTER(DenoiseParams)] + [C.POINTER(C.c_float)] * 6),
     "rtw_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(_P)]),

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <mutex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1025,7 +1026,8 @@ __device__ __forceinline__ void from_ray(Hit& h, const Ray& r, V3 pos, V3 sn, fl
     h.u = u;
     h.v = v;
 }
-template <class TB>
+// UV (cast_kernel): a sphere's (u, v) always, for the caller to read; the render kernels take the default
+template <class TB, bool UV = false>
 __device__ __forceinline__ void leaf_record(const DWorld& w, int leaf, const Ray& r, float t, Hit& h,
                                             const TB& S) {
     const int4 info = leaf_info_of(w, S, leaf);
@@ -1047,7 +1049,7 @@ __device__ __forceinline__ void leaf_record(const DWorld& w, int leaf, const Ray
         // uv (vec3.rs:241-249) only reaches the image through an image texture; a pure function
         // of the normal, so skipping it where no image texture can read it changes nothing
         float u = 0.0f, v = 0.0f;
-        if (flags & RTW_DLEAF_UV) {
+        if (UV || (flags & RTW_DLEAF_UV)) {
             const float theta = TB::gen ? d_acosf_inl(sn.y) : d_acosf(sn.y);
             const float phi = (TB::gen ? d_atan2f_inl(-sn.z, sn.x) : d_atan2f(-sn.z, sn.x)) + F32_PI;
             u = div_c(phi, F32_TAU, 1.0f / F32_TAU);
@@ -4004,6 +4006,124 @@ __global__ void aov_resolve_kernel(const float* __restrict__ planes, const uint3
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// ray queries (rtw_cast_device / rtw_occluded_device, rtw.h): the caller's rays
+// ---------------------------------------------------------------------------------------------
+// One ray per lane, aov_kernel's walk with the range as data: [t_start, the ray's own t_end), the stream
+// (seed, ray index, stream) of the ray's own for volume leaves.  It walks the reference tree, like aov_kernel: the
+// reference tree's cull constants treat every wrapped leaf as uncullable (rtw_cull_prepare), so the cull holds at
+// any ray time, where the SAH tree's wrapped-leaf boxes are swept over the camera's shutter only -- and its ties
+// are the reference's.  ANY (the occlusion call): the same walk in the same order, left at the first accepted
+// leaf; te has not moved until then, so its steps and stream draws are a prefix of the closest-hit walk's and
+// "some leaf accepts" is "the closest-hit walk finds a leaf".
+// A ray is two 16-byte loads ({origin, time}, {direction, t_end}), a record three 16-byte stores ({t, leaf,
+// position.xy}, {position.z, normal}, {uv, front_face, material}), the occlusion answer a byte store.
+struct CastArgs {
+    DWorld w;
+    const float4* rays;  // 2 per ray
+    float4* hits;        // 3 per ray (closest hit)
+    float* albedo;       // 3 per ray (ALBEDO)
+    uint8_t* any;        // 1 per ray (ANY)
+    uint32_t n;          // rays, <= 2^31 - 1
+    int32_t mk_world;
+    float t_start;
+    uint32_t stream;
+    uint64_t seed_key;
+};
+template <bool ANY, bool ALBEDO>
+__global__ __launch_bounds__(RTW_AOV_BLOCK) void cast_kernel(CastArgs A) {
+    const DWorld& w = A.w;
+    const uint32_t i = blockIdx.x * RTW_AOV_BLOCK + threadIdx.x;  // (the grid is ceil(n / 256) <= 2^23 blocks)
+    if (i >= A.n) return;  // (no barrier below)
+    const float4 r0 = A.rays[2 * (size_t)i], r1 = A.rays[2 * (size_t)i + 1];
+    Ray ray;
+    ray.o = v3(r0.x, r0.y, r0.z);
+    ray.time = r0.w;
+    ray.d = v3(r1.x, r1.y, r1.z);
+    const float ts = A.t_start;
+    const ShadeTabs S{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
+    int32_t* stack = reinterpret_cast<int32_t*>(smem) + threadIdx.x;
+    Stats st;
+    rtw_xoro rng = rtw_sample_stream(A.seed_key, i, A.stream);
+    const RayPre rp = ray_pre(ray, A.mk_world != 0);
+    const uint32_t sgn = (ray.d.x > 0.0f ? 1u : 0u) | (ray.d.y > 0.0f ? 2u : 0u) | (ray.d.z > 0.0f ? 4u : 0u);
+    float te = r1.w;
+    int32_t found = -1, node = w.root, sp = 0;
+    bool live = true;
+    while (live) {
+        if (node < 0) {  // a leaf is never box-tested (hittable.rs:436-437)
+            const int32_t leaf = -1 - node;
+            const float4 rec = w.leaf_fast[leaf];
+            float t;
+            bool hit;
+            if (rec.w == rec.w) {  // a plain sphere
+                hit = sphere_t(rec, ray, ts, te, t);
+            } else if (__float_as_int(rec.x) == 2) {  // a plain rect
+                V3 pos;
+                hit = rect_t(load_rect(w, S, __float_as_int(rec.y)), ray, ts, te, t, pos);
+            } else if (__float_as_int(rec.x) == 1) {  // a plain triangle
+                hit = tri_test(load_tri(w.tri_fast, __float_as_int(rec.y)), ray, ts, te, t);
+            } else {  // wrapped leaves, boxes, volumes
+                hit = leaf_t<false, true>(w, S, leaf, ray, ts, te, rng, t, st);
+            }
+            if (hit) {
+                te = t;
+                found = leaf;
+            }
+            if ((ANY && hit) || sp == 0) live = false;
+            else node = stack[(--sp) * RTW_AOV_BLOCK];
+        }
+        if (live && node >= 0) {
+            const float4 nb = w.node_b[node];
+            if (node_pass(w.node_a[node], nb, w.node_km[node], ray, rp, ts, te)) {
+                const int32_t lbits = __float_as_int(nb.z);
+                const int32_t left = lbits >> 2, right = __float_as_int(nb.w);
+                const bool fwd = ((sgn >> (lbits & 3)) & 1u) != 0u;  // ray.d[axis] > 0: left is the near child
+                stack[(sp++) * RTW_AOV_BLOCK] = fwd ? right : left;
+                node = fwd ? left : right;
+            } else if (sp == 0) {
+                live = false;
+            } else {
+                node = stack[(--sp) * RTW_AOV_BLOCK];
+            }
+        }
+    }
+    if (ANY) {
+        A.any[i] = found >= 0 ? (uint8_t)1 : (uint8_t)0;
+        return;
+    }
+    // a miss: t is the ray's own t_end, leaf and material -1, +0 elsewhere
+    float4 h0 = make_float4(te, __int_as_float(-1), 0.0f, 0.0f), h1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f),
+           h2 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+    V3 a = v3(1.0f, 1.0f, 1.0f);
+    if (found >= 0) {
+        Hit h;
+        leaf_record<ShadeTabs, true>(w, found, ray, te, h, S);
+        h0 = make_float4(te, __int_as_float(found), h.pos.x, h.pos.y);
+        h1 = make_float4(h.pos.z, h.n.x, h.n.y, h.n.z);
+        h2 = make_float4(h.u, h.v, __int_as_float(h.front ? 1 : 0), __int_as_float(h.material));
+        if (ALBEDO) {  // aov_kernel's value
+            const int4 M = w.materials[h.material];
+            if ((M.x & (RTW_DMAT_IMAGE - 1)) != RTW_MAT_DIELECTRIC) {
+                const V3 tc = (M.x & RTW_DMAT_IMAGE) != 0
+                                  ? image_texel<false>(w, M.z, (int32_t)((uint32_t)M.w >> 16), M.w & 0xFFFF, h, st)
+                                  : texture_sample<false, TX_ANY>(w, M.y, h, st, S);
+                a = add(v3(0.0f, 0.0f, 0.0f), conv(v3(1.0f, 1.0f, 1.0f), tc));
+            }
+        }
+    }
+    float4* out = A.hits + 3 * (size_t)i;
+    out[0] = h0;
+    out[1] = h1;
+    out[2] = h2;
+    if (ALBEDO) {
+        float* ao = A.albedo + 3 * (size_t)i;
+        ao[0] = a.x;
+        ao[1] = a.y;
+        ao[2] = a.z;
+    }
+}
+
 __global__ void eval_scalar_kernel(int fn, const float* a, const float* b, int64_t n, float* out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -4548,6 +4668,20 @@ struct rtw_gpu_world {
     std::vector<struct rtw_aov*> aovs;      // live AOV accumulators, likewise (aov_orphan)
 };
 
+// The uploaded worlds that have not been released.  The ray queries take a world handle and no object of their own
+// that rtw_world_release could orphan, so they ask here and refuse a released handle by name.
+static std::mutex g_live_mutex;
+static std::vector<const rtw_gpu_world*> g_live_worlds;
+static void world_live(const rtw_gpu_world* g, bool live) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    if (live) g_live_worlds.push_back(g);
+    else g_live_worlds.erase(std::remove(g_live_worlds.begin(), g_live_worlds.end(), g), g_live_worlds.end());
+}
+static bool world_is_live(const rtw_gpu_world* g) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    return std::find(g_live_worlds.begin(), g_live_worlds.end(), g) != g_live_worlds.end();
+}
+
 // experiment builds (-DRTW_WAVE_TIMING): per-wave start / end / queue-empty wall clocks (100 MHz) of
 // the last launch (tools/wave_timing.py; the first launch's queue-empty stamps are not valid)
 extern "C" RTW_API int rtw_debug_wave_times(unsigned long long* out24576) {
@@ -4976,6 +5110,7 @@ extern "C" RTW_API int rtw_world_upload(const rtw_world* w, int device, rtw_gpu_
         delete g;
         return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
     }
+    world_live(g, true);
     *out = g;
     return RTW_OK;
 }
@@ -5189,6 +5324,7 @@ static void aov_orphan(struct rtw_aov* a);
 
 extern "C" RTW_API int rtw_world_release(rtw_gpu_world* g) {
     if (!g) return RTW_OK;
+    world_live(g, false);
     (void)hipSetDevice(g->device);
     for (struct rtw_accum* a : g->accums) accum_orphan(a);
     for (struct rtw_aov* a : g->aovs) aov_orphan(a);
@@ -6881,6 +7017,128 @@ extern "C" RTW_API int rtw_aov_hits(rtw_aov* a, uint32_t* d_out, void* stream) {
     if (!a->g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the AOV accumulator's world was released");
     if (a->part_count > 1) return aov_refuse_part();
     return aov_resolve(a, 2, nullptr, d_out, (hipStream_t)stream);
+}
+
+// ---- ray queries (rtw.h) ----------------------------------------------------------
+static_assert(sizeof(rtw_ray) == 32 && sizeof(rtw_hit) == 48, "cast_kernel moves a ray as 2 and a record as 3 float4");
+namespace {
+// the refusals of both calls, parameters before the world; *launch: there is something to trace
+// (aligned: the device buffers, which the kernel moves 16 bytes at a time; host arrays are staged)
+int cast_check(const rtw_gpu_world* g, const rtw_cast_params* p, bool any, bool aligned, const void* d_rays, int64_t n,
+               const void* d_out, const float* d_albedo, bool* launch) {
+    const uint32_t known_flags = any ? 0u : RTW_CAST_ALBEDO;
+    const char* out_name = any ? "out" : "hits";
+    *launch = false;
+    if (!p) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null params");
+    if (p->flags & ~known_flags) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_cast_params.flags holds an unknown bit");
+    if (p->reserved0 != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_cast_params.reserved0 must be 0");
+    if (!std::isfinite(p->t_start)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_cast_params.t_start must be finite");
+    if (n < 0 || n > (int64_t)0x7FFFFFFF) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "n must be within 0 .. 2^31 - 1");
+    if (!d_rays) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null rays");
+    if (!d_out) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("null ") + out_name);
+    if ((p->flags & RTW_CAST_ALBEDO) && !d_albedo)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null albedo (rtw_cast_params.flags holds RTW_CAST_ALBEDO)");
+    if (!(p->flags & RTW_CAST_ALBEDO) && d_albedo)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "albedo given, but rtw_cast_params.flags does not hold RTW_CAST_ALBEDO");
+    if (aligned && ((uintptr_t)d_rays & 15u) != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rays must be 16-byte aligned");
+    if (aligned && !any && ((uintptr_t)d_out & 15u) != 0)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string(out_name) + " must be 16-byte aligned");
+    if (!g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null world");
+    if (!world_is_live(g)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the world's device state was released");
+    *launch = n > 0;
+    return RTW_OK;
+}
+CastArgs cast_args(const rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* d_rays, int64_t n) {
+    CastArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.w = g->w;
+    A.rays = reinterpret_cast<const float4*>(d_rays);
+    A.n = (uint32_t)n;
+    A.mk_world = g->mk_world;
+    A.t_start = p->t_start;
+    A.stream = p->stream;
+    A.seed_key = rtw_seed_key(p->seed);
+    return A;
+}
+// the stack: one int32_t per level of the reference tree and lane, as rtw_aov_add's
+size_t cast_lds(const rtw_gpu_world* g) { return (size_t)std::max(1, g->depth) * RTW_AOV_BLOCK * sizeof(int32_t); }
+}  // namespace
+
+extern "C" RTW_API int rtw_cast_device(rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* d_rays, int64_t n,
+                                       rtw_hit* d_hits, float* d_albedo, void* stream) {
+    bool launch;
+    if (int rc = cast_check(g, p, false, true, d_rays, n, d_hits, d_albedo, &launch)) return rc;
+    if (!launch) return RTW_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    CastArgs A = cast_args(g, p, d_rays, n);
+    A.hits = reinterpret_cast<float4*>(d_hits);
+    A.albedo = d_albedo;
+    const dim3 grid((unsigned)((n + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK)), block(RTW_AOV_BLOCK);
+    if (d_albedo) hipLaunchKernelGGL((cast_kernel<false, true>), grid, block, cast_lds(g), (hipStream_t)stream, A);
+    else hipLaunchKernelGGL((cast_kernel<false, false>), grid, block, cast_lds(g), (hipStream_t)stream, A);
+    HIP_TRY(hipGetLastError());
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_occluded_device(rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* d_rays, int64_t n,
+                                           uint8_t* d_out, void* stream) {
+    bool launch;
+    if (int rc = cast_check(g, p, true, true, d_rays, n, d_out, nullptr, &launch)) return rc;
+    if (!launch) return RTW_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    CastArgs A = cast_args(g, p, d_rays, n);
+    A.any = d_out;
+    const dim3 grid((unsigned)((n + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK)), block(RTW_AOV_BLOCK);
+    hipLaunchKernelGGL((cast_kernel<true, false>), grid, block, cast_lds(g), (hipStream_t)stream, A);
+    HIP_TRY(hipGetLastError());
+    return RTW_OK;
+}
+
+namespace {
+// host arrays: upload the rays, the device call, copy back (synchronous, the default stream)
+int cast_host(rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* rays, int64_t n, rtw_hit* hits, float* albedo,
+              uint8_t* out, bool any) {
+    bool launch;
+    if (int rc = cast_check(g, p, any, false, rays, n, any ? (const void*)out : (const void*)hits, albedo, &launch)) return rc;
+    if (!launch) return RTW_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    const size_t un = (size_t)n, ray_bytes = un * sizeof(rtw_ray);
+    // one allocation: rays, then records (+ albedo) or bytes; every section starts 16-byte aligned
+    const size_t hit_bytes = any ? 0 : un * sizeof(rtw_hit);
+    const size_t alb_bytes = albedo ? un * 3 * sizeof(float) : 0, any_bytes = any ? un : 0;
+    char* d = nullptr;
+    hipError_t e = hipMalloc(&d, ray_bytes + hit_bytes + alb_bytes + any_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    rtw_ray* d_rays = reinterpret_cast<rtw_ray*>(d);
+    rtw_hit* d_hits = reinterpret_cast<rtw_hit*>(d + ray_bytes);
+    float* d_alb = reinterpret_cast<float*>(d + ray_bytes + hit_bytes);
+    uint8_t* d_any = reinterpret_cast<uint8_t*>(d + ray_bytes);
+    e = hipMemcpy(d_rays, rays, ray_bytes, hipMemcpyHostToDevice);
+    int rc = RTW_OK;
+    if (e == hipSuccess)
+        rc = any ? rtw_occluded_device(g, p, d_rays, n, d_any, nullptr)
+                 : rtw_cast_device(g, p, d_rays, n, d_hits, albedo ? d_alb : nullptr, nullptr);
+    if (rc == RTW_OK && e == hipSuccess) e = hipDeviceSynchronize();
+    if (rc == RTW_OK && e == hipSuccess && any) e = hipMemcpy(out, d_any, any_bytes, hipMemcpyDeviceToHost);
+    if (rc == RTW_OK && e == hipSuccess && !any) e = hipMemcpy(hits, d_hits, hit_bytes, hipMemcpyDeviceToHost);
+    if (rc == RTW_OK && e == hipSuccess && albedo) e = hipMemcpy(albedo, d_alb, alb_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (rc != RTW_OK) return rc;
+    if (e != hipSuccess) return rtw::fail(RTW_ERR_HIP, std::string("rtw_cast: ") + hipGetErrorString(e));
+    return RTW_OK;
+}
+}  // namespace
+
+extern "C" RTW_API int rtw_cast(rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* rays, int64_t n, rtw_hit* hits,
+                                float* albedo) {
+    return cast_host(g, p, rays, n, hits, albedo, nullptr, false);
+}
+
+extern "C" RTW_API int rtw_occluded(rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* rays, int64_t n, uint8_t* out) {
+    return cast_host(g, p, rays, n, nullptr, nullptr, out, true);
 }
 
 // ---- AOV partition records and state (rtw.h; include/rtw_aov_parts.h).  The kernels are rtw_parts.hip's. ----
