@@ -803,6 +803,60 @@ RTW_API int rtw_cast(rtw_gpu_world* gw, const rtw_cast_params* params, const rtw
                      float* albedo);
 RTW_API int rtw_occluded(rtw_gpu_world* gw, const rtw_cast_params* params, const rtw_ray* rays, int64_t n, uint8_t* out);
 
+/* ---- radiance queries: path-traced colour along the caller's rays ----------------------------- */
+/* What colour arrives along a ray of the caller's: an irradiance or reflection probe, a light-map
+ * bake, a camera model of the caller's own, a re-shoot of a frame's noisy rays.  Sample k of ray i is the
+ * reference's ray_color (rendering.rs:19-71; RenderMode::ray_color for RTW_MODE_NORMALS) of that ray -- the whole
+ * path with its materials, textures, volumes and light mixture, in the reference's f32 arithmetic, NaN included --
+ * drawn from the stream rtw_sample_stream(rtw_seed_key(seed), first_ray + i, first_sample + k).  The one stream
+ * serves the walk's volume draws and the shading's draws in ray_color's order.
+ * Every segment, the first included, searches [0.001, +inf): the record's t_end is NOT read, so the rays of a cast
+ * batch can be passed as they are.  The direction need not be unit length and is used as given (reflect, the
+ * dielectric's cos_theta); the background's argument is dot((0, 1, 0), direction) of the caller's ray; time moves
+ * Animation leaves and every scattered ray inherits it.  mode is RTW_MODE_DEFAULT (colours) or RTW_MODE_NORMALS;
+ * max_depth is rtw_render_params' (any int32_t: below 2 a path ends at its first hit).
+ * A sample's value depends on (seed, first_ray + i, first_sample + k) and the ray, and on nothing else in the batch
+ * or the launch: a batch may be split by rays (first_ray) or by samples (first_sample) and resumed.
+ * The reduction: mean[i] = sum / (float)samples per channel, sum from +0.0 over the ray's samples in sample order
+ * (the frame's own expression).  With RTW_RADIANCE_FINITE it is rtw_finite.h's: the sum runs over the samples
+ * rtw_finite_sample keeps, in order, mean[i] = rtw_finite_mean(sum, kept[i]) (+0.0 for kept 0) and kept[i] is
+ * returned -- a probe on a triangle mesh is otherwise NaN wherever a sample met the reference's 0 / 0 pdf.
+ *
+ * Refused with RTW_ERR_INVALID_ARGUMENT and a message naming the field, the parameters before the world, with
+ * nothing launched or written: null params or arrays; flags with an unknown bit (the samples call knows none); a
+ * mode that is no render mode; samples == 0; n < 0 or n > 2^31 - 1; n * samples > 2^31 - 1; first_sample + samples
+ * or first_ray + n past 2^32; kept NULL with RTW_RADIANCE_FINITE or non-NULL without it; device rays that are not
+ * 16-byte aligned; a NULL or released world (as the ray queries above).  n == 0 is RTW_OK with nothing launched.
+ * The rays' own values are device data and are not validated: every walk is bounded by the tree and every path by
+ * max_depth, so a ray with NaN or infinite components returns like any other.
+ * The calls use none of the world's scratch: they interleave freely with frames, accumulators and ray queries.
+ * The *_device calls are asynchronous on `stream`, one launch each; rtw_radiance_resolve_device needs no world
+ * and runs on the current device.  rtw_radiance takes host arrays (any alignment), stages them and waits: it goes
+ * through the batch in chunks of rays against a fixed sample buffer of 256 MiB, chunk c with first_ray + its offset,
+ * so its result is the unchunked one.  (Tests only: the environment variable RTW_RADIANCE_BUFFER_BYTES, read at
+ * each call, replaces the 256 MiB, so that a handful of rays already goes through in several chunks; a chunk
+ * holds at least one ray.  It changes no result.) */
+#define RTW_RADIANCE_FINITE 1u
+typedef struct rtw_radiance_params { /* 32 bytes */
+    uint32_t flags;        /* RTW_RADIANCE_*: read by the resolve and the host call only */
+    int32_t mode;          /* RTW_MODE_DEFAULT / RTW_MODE_NORMALS */
+    int32_t max_depth;     /* as rtw_render_params' */
+    uint32_t samples;      /* >= 1 */
+    uint32_t first_sample;
+    uint32_t first_ray;
+    uint64_t seed;
+} rtw_radiance_params;
+/* d_colors[(i * samples + k) * 3 + c]: the per-sample radiance */
+RTW_API int rtw_radiance_samples_device(rtw_gpu_world* gw, const rtw_radiance_params* params, const rtw_ray* d_rays, int64_t n,
+                                        float* d_colors, void* stream);
+/* d_mean n * 3 floats, d_kept n counts (iff RTW_RADIANCE_FINITE), from d_colors */
+RTW_API int rtw_radiance_resolve_device(const rtw_radiance_params* params, const float* d_colors, int64_t n, float* d_mean,
+                                        uint32_t* d_kept, void* stream);
+RTW_API int rtw_radiance(rtw_gpu_world* gw, const rtw_radiance_params* params, const rtw_ray* rays, int64_t n, float* mean,
+                         uint32_t* kept);
+/* Tests and tools: the number of consecutive work items (samples) a wave of the radiance kernel owns. */
+RTW_API int rtw_debug_radiance_items(void);
+
 /* ---- preview denoiser ---------------------------------------------------------------------- */
 /* A variance-guided a-trous filter for accumulator previews, built on nothing but images:
  * a colour image, the standard error of its channels (rtw_accum_resolve_stderr) and an optional guide of

@@ -7,7 +7,7 @@ Camera.build()..., WorldBuilder / NodeBuilder, demo worlds, rendering.render(...
 """
 from . import image_io
 from .aov import AovAccumulator, AovState, render_aov
-from .cast import CastResult, RayCaster, cast_rays
+from .cast import CastResult, RadianceResult, RayCaster, cast_rays, radiance_rays
 from .denoise import Denoiser, denoise_host
 from .progressive import (
     Accumulator,
@@ -58,6 +58,7 @@ __all__ = [
     "MultiDeviceWorld",
     "NodeBuilder",
     "NodeRef",
+    "RadianceResult",
     "RayCaster",
     "RenderMode",
     "Rng",
@@ -69,6 +70,7 @@ __all__ = [
     "denoise_host",
     "device_count",
     "load_obj_mesh",
+    "radiance_rays",
     "render",
     "render_aov",
     "render_devices",

@@ -278,6 +278,21 @@ class CastParams(C.Structure):  # rtw_cast_params
     ]
 
 
+RADIANCE_FINITE = 1  # RTW_RADIANCE_*
+
+
+class RadianceParams(C.Structure):  # rtw_radiance_params, 32 bytes
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("mode", C.c_int32),
+        ("max_depth", C.c_int32),
+        ("samples", C.c_uint32),
+        ("first_sample", C.c_uint32),
+        ("first_ray", C.c_uint32),
+        ("seed", C.c_uint64),
+    ]
+
+
 class DenoiseParams(C.Structure):  # rtw_denoise_params
     _fields_ = [
         ("width", C.c_int32),
@@ -433,6 +448,10 @@ _SIGS = {
     "rtw_occluded_device": (C.c_int, [_P, C.POINTER(CastParams), _P, C.c_int64, _P, _P]),
     "rtw_cast": (C.c_int, [_P, C.POINTER(CastParams), _P, C.c_int64, _P, _P]),
     "rtw_occluded": (C.c_int, [_P, C.POINTER(CastParams), _P, C.c_int64, _P]),
+    "rtw_radiance_samples_device": (C.c_int, [_P, C.POINTER(RadianceParams), _P, C.c_int64, _P, _P]),
+    "rtw_radiance_resolve_device": (C.c_int, [C.POINTER(RadianceParams), _P, C.c_int64, _P, _P, _P]),
+    "rtw_radiance": (C.c_int, [_P, C.POINTER(RadianceParams), _P, C.c_int64, _P, _P]),
+    "rtw_debug_radiance_items": (C.c_int, []),
     "rtw_denoiser_run_albedo": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
     "rtw_denoise_host_albedo": (C.c_int, [C.POINTER(DenoiseParams)] + [C.POINTER(C.c_float)] * 6),
     "rtw_denoiser_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(_P)]),

@@ -5,6 +5,8 @@ the cursor, a visibility or shadow test between two points, an ambient-occlusion
 bounce.  The hit is the reference's `Scene::hit` over [t_start, t_end), bit for bit: the walk is the first-hit AOV
 pass's, on the reference tree.  Directions need not be unit length; `times` moves Animation leaves and nothing else.
 Volume leaves draw from a stream of the ray's own, (seed, ray index, stream), so a batch is reproducible.
+`RayCaster.radiance` goes on from there (rtw_radiance_*): the reference's ray_color along every ray --
+the whole path -- `samples` times, each sample from the stream (seed, ray index, sample index), and their mean.
 
 numpy arrays in give numpy arrays out (staged through the device, synchronous).  torch tensors on the caster's
 device give device tensors out with no host copy, asynchronously on torch's current stream; the `*_device` methods
@@ -20,7 +22,7 @@ import numpy as np
 
 from . import _native as N
 from ._native import check, lib
-from .rendering import DEFAULT_SEED, DeviceWorld
+from .rendering import DEFAULT_SEED, DeviceWorld, RenderMode
 from .world import World
 
 RAY_WORDS = 8   # rtw_ray: origin, time, direction, t_end
@@ -115,8 +117,51 @@ def _params(t_start, seed, stream, albedo: bool) -> N.CastParams:
     return N.CastParams(N.CAST_ALBEDO if albedo else 0, t_start, int(seed), int(stream), 0)
 
 
+@dataclass
+class RadianceResult:
+    """The radiance of a batch, arrays (or device tensors) over the rays: mean (n, 3); kept (n,) with `finite`, the
+    samples the mean runs over (uint32; int32 as a device tensor); samples (n, S, 3) with `per_sample`."""
+
+    mean: object
+    kept: object = None
+    samples: object = None
+
+    def __len__(self) -> int:
+        return int(self.mean.shape[0])
+
+
+_MAX_ITEMS = (1 << 31) - 1  # rays * samples of one rtw_radiance_samples_device call
+
+
+def _integer(name: str, v, lo: int, hi: int, words: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{name}: {v!r} is not an integer in {words}")
+    return int(v)
+
+
+def _radiance_params(samples, max_depth, mode, seed, first_sample, first_ray, finite, max_bytes, n: int) -> N.RadianceParams:
+    """rtw_radiance_params of a batch of n rays; ValueError naming the argument."""
+    samples = _integer("samples", samples, 1, _MAX_ITEMS, "1 .. 2^31 - 1")
+    max_depth = _integer("max_depth", max_depth, -(1 << 31), (1 << 31) - 1, "-2^31 .. 2^31 - 1")
+    try:
+        mode = RenderMode(mode)
+    except (TypeError, ValueError):
+        raise ValueError(f"mode: {mode!r} is not a RenderMode") from None
+    seed = _integer("seed", seed, 0, (1 << 64) - 1, "0 .. 2^64 - 1")
+    first_sample = _integer("first_sample", first_sample, 0, (1 << 32) - 1, "0 .. 2^32 - 1")
+    if first_sample + samples > 1 << 32:
+        raise ValueError(f"first_sample: {first_sample} + {samples} samples runs past 2^32")
+    first_ray = _integer("first_ray", first_ray, 0, (1 << 32) - 1, "0 .. 2^32 - 1")
+    if first_ray + n > 1 << 32:
+        raise ValueError(f"first_ray: {first_ray} + {n} rays runs past 2^32")
+    if not isinstance(finite, (bool, np.bool_)):
+        raise ValueError(f"finite: {finite!r} is not a bool")
+    _integer("max_bytes", max_bytes, 1, (1 << 63) - 1, "1 .. 2^63 - 1")
+    return N.RadianceParams(N.RADIANCE_FINITE if finite else 0, int(mode), max_depth, samples, first_sample, first_ray, seed)
+
+
 class RayCaster:
-    """Closest-hit and occlusion queries against one World on one GPU.
+    """Closest-hit, occlusion and radiance queries against one World on one GPU.
 
     world: a `World` (uploaded here) or a `DeviceWorld` (shared with frames and accumulators, which the queries
     leave alone: they use none of the world's scratch)."""
@@ -247,6 +292,85 @@ class RayCaster:
         out = np.zeros(n, np.uint8)
         check(lib().rtw_occluded(self._handle(), C.byref(p), C.c_void_p(rays.ctypes.data), n, C.c_void_p(out.ctypes.data)))
         return out != 0
+
+
+    # ---- radiance: ray_color along the rays ------------------------------------------------------
+    def _radiance(self, rays, n: int, p: N.RadianceParams, per_sample: bool, max_bytes: int) -> RadianceResult:
+        """The batch of packed device rays through rtw_radiance_samples_device / rtw_radiance_resolve_device in chunks
+        of rays, chunk c with first_ray + its offset: the unchunked call's bits."""
+        import torch
+
+        dev, S = rays.device, int(p.samples)
+        finite = bool(p.flags & N.RADIANCE_FINITE)
+        mean = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        kept = torch.empty(n, dtype=torch.int32, device=dev) if finite else None
+        out = torch.empty((n, S, 3), dtype=torch.float32, device=dev) if per_sample else None
+        chunk = _MAX_ITEMS // S  # (>= 1: _radiance_params)
+        if not per_sample:
+            chunk = max(1, min(chunk, max_bytes // (S * 12)))
+        chunk = min(chunk, n)
+        scratch = None if per_sample or not n else torch.empty((chunk, S, 3), dtype=torch.float32, device=dev)
+        L, h, sp = lib(), self._handle(), C.c_void_p(self._stream() or 0)
+        for at in range(0, n, max(chunk, 1)):
+            m = min(chunk, n - at)
+            q = N.RadianceParams(0, p.mode, p.max_depth, S, p.first_sample, p.first_ray + at, p.seed)
+            colors = out[at:at + m] if per_sample else scratch
+            check(L.rtw_radiance_samples_device(h, C.byref(q), C.c_void_p(rays[at:].data_ptr()), m, C.c_void_p(colors.data_ptr()), sp))
+            q.flags = p.flags
+            check(L.rtw_radiance_resolve_device(C.byref(q), C.c_void_p(colors.data_ptr()), m, C.c_void_p(mean[at:].data_ptr()),
+                                                C.c_void_p(kept[at:].data_ptr()) if finite else None, sp))
+        return RadianceResult(mean=mean, kept=kept, samples=out)
+
+    def radiance_device(self, origins, directions, times=None, samples: int = 16, max_depth: int = 50,
+                        mode: RenderMode = RenderMode.Default, seed: int = DEFAULT_SEED, first_sample: int = 0,
+                        first_ray: int = 0, finite: bool = False, per_sample: bool = False,
+                        max_bytes: int = 256 << 20) -> RadianceResult:
+        """`radiance` for float32 tensors on the caster's device (scalars and (3,) vectors are broadcast): device
+        tensors out, no host copy, asynchronous on torch's current stream."""
+        rays = self._pack_device(origins, directions, times, None)
+        n = int(rays.shape[0])
+        p = _radiance_params(samples, max_depth, mode, seed, first_sample, first_ray, finite, max_bytes, n)
+        return self._radiance(rays, n, p, bool(per_sample), int(max_bytes))
+
+    def radiance(self, origins, directions, times=None, samples: int = 16, max_depth: int = 50,
+                 mode: RenderMode = RenderMode.Default, seed: int = DEFAULT_SEED, first_sample: int = 0, first_ray: int = 0,
+                 finite: bool = False, per_sample: bool = False, max_bytes: int = 256 << 20) -> RadianceResult:
+        """The path-traced colour that arrives along every ray: `samples` samples of the reference's ray_color each
+        (the whole path: materials, textures, volumes, the light mixture), sample k of ray i drawn from the stream
+        (seed, first_ray + i, first_sample + k), and their mean in sample order.  Every segment searches
+        [0.001, +inf): there is no t_end.  Directions need not be unit length; times (default 0) moves Animation
+        leaves along the whole path.  finite: the mean over the samples without a NaN or infinite channel, and
+        `kept`, their count (a probe on a triangle mesh is otherwise NaN where the reference divides 0 by 0).
+        per_sample: `samples` (n, S, 3) too.  Without it the samples live in a scratch tensor of at most max_bytes
+        and the batch goes through in chunks of rays, with the same bits.  A batch split by rays (first_ray) or by
+        samples (first_sample) gives the same samples.  Raises ValueError naming the argument, RtwError for what
+        the library refuses."""
+        if any(_is_tensor(a) for a in (origins, directions, times)):
+            return self.radiance_device(origins, directions, times, samples, max_depth, mode, seed, first_sample, first_ray,
+                                        finite, per_sample, max_bytes)
+        import torch
+
+        rays = pack_rays(origins, directions, times, None)
+        n = rays.shape[0]
+        p = _radiance_params(samples, max_depth, mode, seed, first_sample, first_ray, finite, max_bytes, n)
+        d_rays = torch.from_numpy(rays).to(torch.device("cuda", self.device))
+        res = self._radiance(d_rays, n, p, bool(per_sample), int(max_bytes))
+        return RadianceResult(mean=res.mean.cpu().numpy(), kept=None if res.kept is None else res.kept.cpu().numpy().view(np.uint32),
+                              samples=None if res.samples is None else res.samples.cpu().numpy())
+
+
+def radiance_rays(world, origins, directions, times=None, samples: int = 16, max_depth: int = 50,
+                  mode: RenderMode = RenderMode.Default, seed: int = DEFAULT_SEED, first_sample: int = 0, first_ray: int = 0,
+                  finite: bool = False, per_sample: bool = False, max_bytes: int = 256 << 20, device: int = 0) -> RadianceResult:
+    """One batch of `RayCaster.radiance` against `world` (a World is uploaded for the call and released after it; a
+    DeviceWorld is used and left alone)."""
+    caster = RayCaster(world, device)
+    try:
+        return caster.radiance(origins, directions, times, samples, max_depth, mode, seed, first_sample, first_ray, finite,
+                               per_sample, max_bytes)
+    finally:
+        if not isinstance(world, DeviceWorld):
+            caster.release()
 
 
 def cast_rays(world, origins, directions, times=None, t_end=None, *, t_start: float = 0.001, seed: int = DEFAULT_SEED,

@@ -4124,6 +4124,177 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void cast_kernel(CastArgs A) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// radiance queries (rtw_radiance_samples_device / rtw_radiance_resolve_device, rtw.h): ray_color
+// along the caller's rays
+// ---------------------------------------------------------------------------------------------
+// Work item j = i * samples + k is sample k of ray i: one whole path, cast_kernel's walk over [0.001, +inf) and
+// shade() by turns, volume draws and shading draws from the one stream (seed, first_ray + i, first_sample + k) in
+// ray_color's order.  Neighbouring items are samples of one ray: the first segment is coherent and the ray's load
+// a broadcast.
+// Paths differ in length, so a wave owns RTW_RAD_ITEMS consecutive items and a lane whose path has ended takes
+// the next unstarted one: the ballot of the idle lanes, a lane's rank among them (mbcnt), and a cursor that every
+// lane advances by the ballot's population -- wave-uniform, so it lives in a scalar register.  Nothing is shared
+// between waves: no atomic, no barrier, no counter in memory to reset, no wait; concurrent launches share nothing.
+// A round of the wave loop: idle lanes start an item; every busy lane walks one segment to its end and shades it;
+// a finished lane stores its three floats and is idle.  The walk is bounded by the tree, a path has at most
+// max(1, max_depth) segments (shade ends it at a hit with depth <= 1), and every round ends a segment of every
+// busy lane: at most RTW_RAD_ITEMS * max(1, max_depth) rounds.  Lanes past the launch's items start nothing and
+// touch no memory; a wave whose range starts past them returns at once.
+// (The constant: tools/radiance_bench.py's sweep, profiles/r24/radiance_bench.txt.  64 is "no refill", the same code.)
+#ifndef RTW_RAD_ITEMS
+#define RTW_RAD_ITEMS 256
+#endif
+static_assert(RTW_RAD_ITEMS >= 64 && RTW_RAD_ITEMS % 64 == 0, "a wave's range is whole waves of items");
+struct RadArgs {
+    DWorld w;
+    const DWorld* wdev;  // shade()'s copy of `w` in device memory
+    const float4* rays;  // 2 per ray; t_end is not read
+    float* colors;       // 3 per item
+    uint32_t items;      // n * samples, <= 2^31 - 1
+    uint32_t samples;
+    uint32_t first_sample, first_ray;
+    int32_t mode, max_depth, mk_world;
+    uint64_t seed_key;
+};
+__global__ __launch_bounds__(RTW_AOV_BLOCK) void radiance_kernel(RadArgs A) {
+    const DWorld& w = A.w;
+    // (the grid is ceil(items / (4 * RTW_RAD_ITEMS)) blocks: wave * RTW_RAD_ITEMS < items + 4 * RTW_RAD_ITEMS < 2^32)
+    uint32_t cursor = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int32_t)((blockIdx.x * (RTW_AOV_BLOCK / 64) + (threadIdx.x >> 6)) * (uint32_t)RTW_RAD_ITEMS));
+    if (cursor >= A.items) return;  // wave-uniform (no barrier below)
+    const uint32_t end = min(cursor + (uint32_t)RTW_RAD_ITEMS, A.items);
+    const ShadeTabs S{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
+    int32_t* stack = reinterpret_cast<int32_t*>(smem) + threadIdx.x;
+    Stats st;
+    Path P;
+    P.ray.o = P.ray.d = P.att = P.acc = v3(0.0f, 0.0f, 0.0f);
+    P.ray.time = 0.0f;
+    P.depth = 0;
+    P.rng = rtw_xoro{0, 0};
+    float pdot = 0.0f;
+    uint32_t item = 0;
+    bool busy = false;
+    // The proximity cull's sphere bound (rtw_cull.h) is the reference sphere test's error for a direction of unit
+    // length up to rounding, which every direction the renderer makes is (Camera::ray, shade()).  The caller's need
+    // not be, and the reference's sphere test then accepts roots whose points are nowhere near the sphere: a first
+    // segment whose |d|^2 is not within 8u of 1 walks with k = +inf, hit_cond alone (RTW_NO_CULL's walk), as the
+    // oracle does.  Within 8u the bound's k term takes 4u t^2 / r more of its 64u t^2 / r.
+    bool cull = true;
+    for (;;) {
+        // 1. idle lanes take the next unstarted items of the wave's range, in lane order
+        const unsigned long long idle = __ballot(!busy);
+        if (idle != 0ull && cursor < end) {  // (wave-uniform)
+            if (!busy) {
+                const uint32_t j = cursor + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (j < end) {
+                    const uint32_t i = j / A.samples, k = j - i * A.samples;
+                    const float4 r0 = A.rays[2 * (size_t)i], r1 = A.rays[2 * (size_t)i + 1];
+                    P.ray.o = v3(r0.x, r0.y, r0.z);
+                    P.ray.time = r0.w;
+                    P.ray.d = v3(r1.x, r1.y, r1.z);
+                    P.att = v3(1.0f, 1.0f, 1.0f);
+                    P.acc = v3(0.0f, 0.0f, 0.0f);
+                    P.depth = A.max_depth;
+                    P.rng = rtw_sample_stream(A.seed_key, A.first_ray + i, A.first_sample + k);
+                    pdot = dot(v3(0.0f, 1.0f, 0.0f), P.ray.d);  // background_color.rs:13 on the caller's ray
+                    cull = __builtin_fabsf(dot(P.ray.d, P.ray.d) - 1.0f) <= 0x1p-21f;
+                    item = j;
+                    busy = true;
+                }
+            }
+            cursor = min(end, cursor + (uint32_t)__popcll(idle));
+        }
+        if (__ballot(busy) == 0ull) break;  // (then cursor == end: a round with items left starts at least one)
+        if (busy) {
+            // 2. one segment to its end: cast_kernel's walk over [0.001, +inf), the path's stream for volume leaves
+            const Ray ray = P.ray;
+            const RayPre rp = ray_pre(ray, A.mk_world != 0);
+            const uint32_t sgn = (ray.d.x > 0.0f ? 1u : 0u) | (ray.d.y > 0.0f ? 2u : 0u) | (ray.d.z > 0.0f ? 4u : 0u);
+            float te = F32_INF;
+            int32_t found = -1, node = w.root, sp = 0;
+            bool live = true;
+            while (live) {
+                if (node < 0) {  // a leaf is never box-tested (hittable.rs:436-437)
+                    const int32_t leaf = -1 - node;
+                    const float4 rec = w.leaf_fast[leaf];
+                    float t;
+                    bool hit;
+                    if (rec.w == rec.w) {  // a plain sphere
+                        hit = sphere_t(rec, ray, 0.001f, te, t);
+                    } else if (__float_as_int(rec.x) == 2) {  // a plain rect
+                        V3 pos;
+                        hit = rect_t(load_rect(w, S, __float_as_int(rec.y)), ray, 0.001f, te, t, pos);
+                    } else if (__float_as_int(rec.x) == 1) {  // a plain triangle
+                        hit = tri_test(load_tri(w.tri_fast, __float_as_int(rec.y)), ray, 0.001f, te, t);
+                    } else {  // wrapped leaves, boxes, volumes
+                        hit = leaf_t<false, true>(w, S, leaf, ray, 0.001f, te, P.rng, t, st);
+                    }
+                    if (hit) {
+                        te = t;
+                        found = leaf;
+                    }
+                    if (sp == 0) live = false;
+                    else node = stack[(--sp) * RTW_AOV_BLOCK];
+                }
+                if (live && node >= 0) {
+                    const float4 nb = w.node_b[node];
+                    const float2 km = cull ? w.node_km[node] : make_float2(F32_INF, 0.0f);
+                    if (node_pass(w.node_a[node], nb, km, ray, rp, 0.001f, te)) {
+                        const int32_t lbits = __float_as_int(nb.z);
+                        const int32_t left = lbits >> 2, right = __float_as_int(nb.w);
+                        const bool fwd = ((sgn >> (lbits & 3)) & 1u) != 0u;  // ray.d[axis] > 0: left is the near child
+                        stack[(sp++) * RTW_AOV_BLOCK] = fwd ? right : left;
+                        node = fwd ? left : right;
+                    } else if (sp == 0) {
+                        live = false;
+                    } else {
+                        node = stack[(--sp) * RTW_AOV_BLOCK];
+                    }
+                }
+            }
+            cull = true;  // (every later segment's direction is shade()'s)
+            // 3. one bounce of ray_color (rendering.rs:19-71)
+            const ShadeOut so = shade<false, TX_ANY>(A.wdev, A.mode, P, found, te, pdot, S);
+            P = so.p;
+            // 4. a finished path stores its radiance; the lane is idle
+            if (so.done) {
+                float* o = A.colors + 3 * (size_t)item;
+                o[0] = so.color.x;
+                o[1] = so.color.y;
+                o[2] = so.color.z;
+                busy = false;
+            }
+        }
+    }
+}
+// One lane per ray: accumulate_kernel's in-order sum over the ray's samples, colors[(i * samples + k) * 3 + c], from
+// +0.0, and its last step, divs(sum, (float)samples).  FINITE (RTW_RADIANCE_FINITE, rtw_finite.h): the sum runs over
+// the samples rtw_finite_sample keeps, the mean is rtw_finite_mean(sum, kept), and kept[i] is stored.
+template <bool FINITE>
+__global__ void radiance_resolve_kernel(const float* __restrict__ colors, uint32_t n, uint32_t samples,
+                                        float* __restrict__ mean, uint32_t* __restrict__ kept) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* c = colors + 3 * ((size_t)i * samples);
+    V3 sum = v3(0.0f, 0.0f, 0.0f);
+    uint32_t k = 0;
+    for (uint32_t s = 0; s < samples; ++s, c += 3) {
+        const V3 col = v3(c[0], c[1], c[2]);
+        if (FINITE && !rtw_finite_sample(col.x, col.y, col.z)) continue;  // (a branch, as accumulate_body's)
+        sum = add(sum, col);
+        ++k;
+    }
+    const V3 r = FINITE ? v3(rtw_finite_mean(sum.x, k), rtw_finite_mean(sum.y, k), rtw_finite_mean(sum.z, k))
+                        : divs(sum, (float)samples);
+    float* o = mean + 3 * (size_t)i;
+    o[0] = r.x;
+    o[1] = r.y;
+    o[2] = r.z;
+    if (FINITE) kept[i] = k;
+}
+
 __global__ void eval_scalar_kernel(int fn, const float* a, const float* b, int64_t n, float* out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -7139,6 +7310,139 @@ extern "C" RTW_API int rtw_cast(rtw_gpu_world* g, const rtw_cast_params* p, cons
 
 extern "C" RTW_API int rtw_occluded(rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* rays, int64_t n, uint8_t* out) {
     return cast_host(g, p, rays, n, nullptr, nullptr, out, true);
+}
+
+// ---- radiance queries (rtw.h) -----------------------------------------------------
+static_assert(sizeof(rtw_radiance_params) == 32, "rtw_radiance_params is 32 bytes");
+namespace {
+// rtw_radiance's sample buffer: a chunk of rays holds at most this many bytes of samples (and at least one ray)
+constexpr size_t kRadianceChunkBytes = (size_t)256 << 20;
+// The refusals of the three calls, parameters before the world (`world`: the call takes one).  known_flags: the
+// samples call knows none.  Each call names its own arrays: a (rays or colors), b (colors or mean).
+int radiance_check(const rtw_radiance_params* p, uint32_t known_flags, int64_t n, const char* a_name, const void* a,
+                   const char* b_name, const void* b, bool takes_kept, const uint32_t* kept, bool aligned_rays, bool world,
+                   const rtw_gpu_world* g, bool* launch) {
+    *launch = false;
+    if (!p) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null params");
+    if (p->flags & ~known_flags) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_radiance_params.flags holds an unknown bit");
+    if (p->mode != RTW_MODE_DEFAULT && p->mode != RTW_MODE_NORMALS)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_radiance_params.mode is not a render mode");
+    if (p->samples == 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_radiance_params.samples must be >= 1");
+    // (max_depth: rtw_render takes any int32_t -- below 2 a path ends at its first hit -- and so do these calls)
+    if (n < 0 || n > (int64_t)0x7FFFFFFF) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "n must be within 0 .. 2^31 - 1");
+    if (n * (int64_t)p->samples > (int64_t)0x7FFFFFFF)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "n * rtw_radiance_params.samples must be within 0 .. 2^31 - 1");
+    if ((uint64_t)p->first_sample + p->samples > ((uint64_t)1 << 32))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_radiance_params.first_sample + samples runs past 2^32");
+    if ((uint64_t)p->first_ray + (uint64_t)n > ((uint64_t)1 << 32))
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rtw_radiance_params.first_ray + n runs past 2^32");
+    if (!a) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("null ") + a_name);
+    if (!b) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, std::string("null ") + b_name);
+    if (takes_kept && (p->flags & RTW_RADIANCE_FINITE) && !kept)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null kept (rtw_radiance_params.flags holds RTW_RADIANCE_FINITE)");
+    if (takes_kept && !(p->flags & RTW_RADIANCE_FINITE) && kept)
+        return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "kept given, but rtw_radiance_params.flags does not hold RTW_RADIANCE_FINITE");
+    if (aligned_rays && ((uintptr_t)a & 15u) != 0) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "rays must be 16-byte aligned");
+    if (world) {
+        if (!g) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "null world");
+        if (!world_is_live(g)) return rtw::fail(RTW_ERR_INVALID_ARGUMENT, "the world's device state was released");
+    }
+    *launch = n > 0;
+    return RTW_OK;
+}
+}  // namespace
+
+// tests and tools: a wave's range of items
+extern "C" RTW_API int rtw_debug_radiance_items(void) { return RTW_RAD_ITEMS; }
+
+extern "C" RTW_API int rtw_radiance_samples_device(rtw_gpu_world* g, const rtw_radiance_params* p, const rtw_ray* d_rays,
+                                                   int64_t n, float* d_colors, void* stream) {
+    bool launch;
+    if (int rc = radiance_check(p, 0u, n, "rays", d_rays, "colors", d_colors, false, nullptr, true, true, g, &launch)) return rc;
+    if (!launch) return RTW_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    RadArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.w = g->w;
+    A.wdev = g->wdev;
+    A.rays = reinterpret_cast<const float4*>(d_rays);
+    A.colors = d_colors;
+    A.items = (uint32_t)(n * (int64_t)p->samples);
+    A.samples = p->samples;
+    A.first_sample = p->first_sample;
+    A.first_ray = p->first_ray;
+    A.mode = p->mode;
+    A.max_depth = p->max_depth;
+    A.mk_world = g->mk_world;
+    A.seed_key = rtw_seed_key(p->seed);
+    constexpr uint32_t per_block = (RTW_AOV_BLOCK / 64) * RTW_RAD_ITEMS;
+    const dim3 grid((A.items + per_block - 1) / per_block), block(RTW_AOV_BLOCK);
+    hipLaunchKernelGGL(radiance_kernel, grid, block, cast_lds(g), (hipStream_t)stream, A);
+    HIP_TRY(hipGetLastError());
+    return RTW_OK;
+}
+
+extern "C" RTW_API int rtw_radiance_resolve_device(const rtw_radiance_params* p, const float* d_colors, int64_t n, float* d_mean,
+                                                   uint32_t* d_kept, void* stream) {
+    bool launch;
+    if (int rc = radiance_check(p, RTW_RADIANCE_FINITE, n, "colors", d_colors, "mean", d_mean, true, d_kept, false, false, nullptr,
+                                &launch))
+        return rc;
+    if (!launch) return RTW_OK;
+    // (the current device: the arrays are the caller's, and the call takes no world to name another)
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (p->flags & RTW_RADIANCE_FINITE)
+        hipLaunchKernelGGL(radiance_resolve_kernel<true>, grid, block, 0, (hipStream_t)stream, d_colors, (uint32_t)n, p->samples,
+                           d_mean, d_kept);
+    else
+        hipLaunchKernelGGL(radiance_resolve_kernel<false>, grid, block, 0, (hipStream_t)stream, d_colors, (uint32_t)n, p->samples,
+                           d_mean, (uint32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    return RTW_OK;
+}
+
+// host arrays: per chunk of rays, upload, trace, resolve, copy back (synchronous, the default stream).  Chunk c
+// passes first_ray + its offset, so its samples -- and the in-order reduction over them -- are the unchunked call's.
+extern "C" RTW_API int rtw_radiance(rtw_gpu_world* g, const rtw_radiance_params* p, const rtw_ray* rays, int64_t n, float* mean,
+                                    uint32_t* kept) {
+    bool launch;
+    if (int rc = radiance_check(p, RTW_RADIANCE_FINITE, n, "rays", rays, "mean", mean, true, kept, false, true, g, &launch)) return rc;
+    if (!launch) return RTW_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    const size_t per_ray = (size_t)p->samples * 3 * sizeof(float);
+    const size_t cap = env_size("RTW_RADIANCE_BUFFER_BYTES", kRadianceChunkBytes);  // (tests: chunks of a few rays)
+    const size_t chunk = std::min((size_t)n, std::max((size_t)1, cap / per_ray));
+    // one allocation: rays, samples, means, kept; every section starts 16-byte aligned
+    const size_t ray_bytes = chunk * sizeof(rtw_ray), col_bytes = (chunk * per_ray + 15) & ~(size_t)15;
+    const size_t mean_bytes = (chunk * 3 * sizeof(float) + 15) & ~(size_t)15, kept_bytes = kept ? chunk * sizeof(uint32_t) : 0;
+    char* d = nullptr;
+    hipError_t e = hipMalloc(&d, ray_bytes + col_bytes + mean_bytes + kept_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return rtw::fail(RTW_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    rtw_ray* d_rays = reinterpret_cast<rtw_ray*>(d);
+    float* d_colors = reinterpret_cast<float*>(d + ray_bytes);
+    float* d_mean = reinterpret_cast<float*>(d + ray_bytes + col_bytes);
+    uint32_t* d_kept = kept ? reinterpret_cast<uint32_t*>(d + ray_bytes + col_bytes + mean_bytes) : nullptr;
+    int rc = RTW_OK;
+    for (size_t at = 0; at < (size_t)n && rc == RTW_OK && e == hipSuccess; at += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - at);
+        rtw_radiance_params q = *p;
+        q.first_ray = p->first_ray + (uint32_t)at;
+        q.flags = 0;  // (the samples call knows no flag)
+        e = hipMemcpy(d_rays, rays + at, m * sizeof(rtw_ray), hipMemcpyHostToDevice);
+        if (e == hipSuccess) rc = rtw_radiance_samples_device(g, &q, d_rays, (int64_t)m, d_colors, nullptr);
+        q.flags = p->flags;
+        if (rc == RTW_OK && e == hipSuccess) rc = rtw_radiance_resolve_device(&q, d_colors, (int64_t)m, d_mean, d_kept, nullptr);
+        if (rc == RTW_OK && e == hipSuccess) e = hipDeviceSynchronize();
+        if (rc == RTW_OK && e == hipSuccess) e = hipMemcpy(mean + 3 * at, d_mean, m * 3 * sizeof(float), hipMemcpyDeviceToHost);
+        if (rc == RTW_OK && e == hipSuccess && kept) e = hipMemcpy(kept + at, d_kept, m * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);
+    if (rc != RTW_OK) return rc;
+    if (e != hipSuccess) return rtw::fail(RTW_ERR_HIP, std::string("rtw_radiance: ") + hipGetErrorString(e));
+    return RTW_OK;
 }
 
 // ---- AOV partition records and state (rtw.h; include/rtw_aov_parts.h).  The kernels are rtw_parts.hip's. ----
