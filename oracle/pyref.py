@@ -59,6 +59,11 @@ class Xoro:
             if res < high:
                 return res
 
+    def gen_bool(self, p: float) -> bool:  # Bernoulli::new(p).sample: p_int = (p * 2^64) as u64, next_u64() < p_int
+        if p == 1.0:  # ALWAYS_TRUE: no draw
+            return True
+        return self.next_u64() < int(p * 18446744073709551616.0)
+
     def gen_range_u32(self, n: int) -> int:  # UniformInt::sample_single_inclusive(0, n-1)
         rng = n & 0xFFFFFFFF
         lz = 32 - rng.bit_length()

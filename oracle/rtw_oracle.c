@@ -648,16 +648,47 @@ static int bvh_closest_leaf_recursive(const Ctx* c, int32_t node, const Ray* r, 
     if (r->dir.e[nd->axis] > 0.0f) return bvh_list_leaf(c, nd->left, nd->right, r, ts, te, h, leaf);
     return bvh_list_leaf(c, nd->right, nd->left, r, ts, te, h, leaf);
 }
-static int world_hit(const Ctx* c, const Ray* r, Hit* h) {
+static int world_hit_leaf(const Ctx* c, const Ray* r, Hit* h, int* leaf) {
     if (c->st) c->st->rays++;
     float end = F32_INF;
-    int leaf = -1;
-    const int ok = bvh_closest_leaf_recursive(c, c->w->root, r, 0.001f, &end, h, &leaf);
-    if (ok) count_hit(c, leaf);
+    *leaf = -1;
+    const int ok = bvh_closest_leaf_recursive(c, c->w->root, r, 0.001f, &end, h, leaf);
+    if (ok) count_hit(c, *leaf);
     return ok;
 }
+static int world_hit(const Ctx* c, const Ray* r, Hit* h) {
+    int leaf;
+    return world_hit_leaf(c, r, h, &leaf);
+}
 
-static V3 ray_color(const Ctx* c, const Ray* ray, int32_t max_depth) {
+/* One loop for ray_color and rtw_oracle_path: `rec` (NULL for the renderer) receives one record per segment,
+ * at most `cap` of them; *count is the number of segments walked.  The arithmetic does not know about it. */
+static void put3(float* o, V3 v) { o[0] = v.e[0]; o[1] = v.e[1]; o[2] = v.e[2]; }
+static rtw_oracle_vertex* vertex_begin(rtw_oracle_vertex* rec, int cap, int* count, const Ctx* c, const Ray* cur) {
+    if (!rec) return NULL;
+    const int k = (*count)++;
+    if (k >= cap) return NULL;
+    rtw_oracle_vertex* v = &rec[k];
+    memset(v, 0, sizeof(*v));
+    v->leaf = -1;
+    v->material = -1;
+    v->state_before[0] = c->rng->s0;
+    v->state_before[1] = c->rng->s1;
+    put3(v->origin, cur->origin);
+    put3(v->dir, cur->dir);
+    v->time = cur->time;
+    return v;
+}
+static void vertex_end(rtw_oracle_vertex* v, const Ctx* c, int end, V3 att, V3 acc) {
+    if (!v) return;
+    v->end = end;
+    put3(v->att, att);
+    put3(v->acc, acc);
+    v->state_after[0] = c->rng->s0;
+    v->state_after[1] = c->rng->s1;
+}
+
+static V3 ray_color_rec(const Ctx* c, const Ray* ray, int32_t max_depth, rtw_oracle_vertex* rec, int cap, int* count) {
     const rtw_world* w = c->w;
     int32_t depth = max_depth;
     V3 att = v3(1.0f, 1.0f, 1.0f);
@@ -665,8 +696,22 @@ static V3 ray_color(const Ctx* c, const Ray* ray, int32_t max_depth) {
     Ray cur = *ray;
     for (;;) {
         Hit h;
-        if (world_hit(c, &cur, &h)) {
-            if (depth <= 1) return v3(0.0f, 0.0f, 0.0f);
+        int leaf = -1;
+        rtw_oracle_vertex* v = vertex_begin(rec, cap, count, c, &cur);
+        if (world_hit_leaf(c, &cur, &h, &leaf)) {
+            if (v) {
+                v->hit = 1;
+                v->leaf = leaf;
+                v->t = h.t;
+                put3(v->position, h.position);
+                put3(v->normal, h.normal);
+                v->front_face = h.front_face;
+                v->material = h.material;
+            }
+            if (depth <= 1) {
+                vertex_end(v, c, RTW_PATH_END_DEPTH, att, emitted_acc);
+                return v3(0.0f, 0.0f, 0.0f);
+            }
             const rtw_material* M = &w->materials[h.material];
             V3 a;
             Dist d;
@@ -700,17 +745,32 @@ static V3 ray_color(const Ctx* c, const Ray* ray, int32_t max_depth) {
                 const V3 e = material_emit(c, M, &h);
                 emitted_acc = vadd(emitted_acc, vconv(att, e));
                 att = vmul(vconv(att, a), prob);
+                if (v) {
+                    v->scatters = 1;
+                    put3(v->scattered, scattered.dir);
+                    put3(v->a, a);
+                    put3(v->e, e);
+                    v->prob = prob;
+                }
+                vertex_end(v, c, RTW_PATH_CONTINUES, att, emitted_acc);
                 cur = scattered;
                 depth -= 1;
                 continue;
             }
             const V3 e = material_emit(c, M, &h);
+            if (v) put3(v->e, e);
+            vertex_end(v, c, RTW_PATH_END_ABSORBED, att, emitted_acc);
             return vadd(emitted_acc, vconv(att, e));
         }
         /* rendering.rs:67: background of the PRIMARY ray */
         const V3 e = background_sample(&w->background, ray);
+        if (v) put3(v->e, e);
+        vertex_end(v, c, RTW_PATH_END_MISS, att, emitted_acc);
         return vadd(emitted_acc, vconv(att, e));
     }
+}
+static V3 ray_color(const Ctx* c, const Ray* ray, int32_t max_depth) {
+    return ray_color_rec(c, ray, max_depth, NULL, 0, NULL);
 }
 
 /* RenderMode::ray_color (rendering.rs:100-119) */
@@ -1024,6 +1084,47 @@ RTW_API int rtw_oracle_ray_color(const rtw_world* w, const float origin[3], cons
     for (int i = 0; i < 3; ++i) color[i] = col.e[i];
     rng_state[0] = rng.s0;
     rng_state[1] = rng.s1;
+    return RTW_OK;
+}
+
+RTW_API int rtw_oracle_path(const rtw_world* w, const float origin[3], const float dir[3], float time,
+                            int32_t max_depth, uint64_t rng_state[2], rtw_oracle_vertex* vertices, int32_t capacity,
+                            int32_t* count, float color[3]) {
+    if (!w || w->leaf_count < 1 || !vertices || capacity < 0 || !count) return RTW_ERR_INVALID_ARGUMENT;
+    rtw_xoro rng = {rng_state[0], rng_state[1]};
+    Ctx c = {w, &rng, NULL, NULL};
+    Ray r;
+    r.origin = vload(origin);
+    r.dir = vload(dir);
+    r.time = time;
+    int n = 0;
+    const V3 col = ray_color_rec(&c, &r, max_depth, vertices, capacity, &n);
+    *count = n;
+    for (int i = 0; i < 3; ++i) color[i] = col.e[i];
+    rng_state[0] = rng.s0;
+    rng_state[1] = rng.s1;
+    return RTW_OK;
+}
+
+/* rtw_oracle_path over n rays (packed origins, directions, times and states), `capacity` records a ray. */
+RTW_API int rtw_oracle_paths(const rtw_world* w, const float* origins, const float* dirs, const float* times,
+                             int64_t n, int32_t max_depth, uint64_t* rng_states, rtw_oracle_vertex* vertices,
+                             int32_t capacity, int32_t* counts, float* colors) {
+    for (int64_t i = 0; i < n; ++i) {
+        const int rc = rtw_oracle_path(w, origins + 3 * i, dirs + 3 * i, times[i], max_depth, rng_states + 2 * i,
+                                       vertices + (size_t)capacity * (size_t)i, capacity, counts + i, colors + 3 * i);
+        if (rc != RTW_OK) return rc;
+    }
+    return RTW_OK;
+}
+
+RTW_API int rtw_oracle_ray_colors(const rtw_world* w, const float* origins, const float* dirs, const float* times,
+                                  int64_t n, int32_t max_depth, uint64_t* rng_states, float* colors) {
+    for (int64_t i = 0; i < n; ++i) {
+        const int rc = rtw_oracle_ray_color(w, origins + 3 * i, dirs + 3 * i, times[i], max_depth, RTW_MODE_DEFAULT,
+                                            rng_states + 2 * i, colors + 3 * i);
+        if (rc != RTW_OK) return rc;
+    }
     return RTW_OK;
 }
 

@@ -56,6 +56,39 @@ RTW_API int rtw_oracle_ray_color(const rtw_world* w, const float origin[3], cons
                                  float time, int32_t max_depth, int32_t mode, uint64_t rng[2],
                                  float color[3]);
 
+/* One segment of ray_color's loop as rtw_oracle_path records it. */
+#define RTW_PATH_CONTINUES 0    /* hit, scattered: the next record is the scattered ray's */
+#define RTW_PATH_END_MISS 1     /* no hit: e = the background along the PRIMARY ray (rendering.rs:67) */
+#define RTW_PATH_END_DEPTH 2    /* hit with depth <= 1: black, the accumulated emission dropped (rendering.rs:26-27) */
+#define RTW_PATH_END_ABSORBED 3 /* hit, no scatter: e = emit (rendering.rs:63-64) */
+typedef struct rtw_oracle_vertex {
+    uint64_t state_before[2]; /* the stream before world_hit */
+    uint64_t state_after[2];  /* ... and when the segment is done */
+    float origin[3], dir[3], time; /* the segment's ray */
+    int32_t hit, leaf;        /* leaf -1: a miss */
+    float t, position[3], normal[3];
+    int32_t front_face, material;
+    int32_t scatters, end;    /* end: RTW_PATH_* */
+    float scattered[3];       /* the scattered direction (scatters only) */
+    float a[3], e[3], prob;   /* attenuation, emitted (or the background at a miss), scattering_pdf / pdf */
+    float att[3], acc[3];     /* accum_attentuation and accum_emitted after the segment */
+    int32_t reserved0;
+} rtw_oracle_vertex;
+
+/* ray_color (rendering.rs:19-71) for one ray, the same loop as rtw_oracle_ray_color's, with a record of every
+ * segment: at most `capacity` are written, *count is the number walked.  color is ray_color's. */
+RTW_API int rtw_oracle_path(const rtw_world* w, const float origin[3], const float dir[3], float time,
+                            int32_t max_depth, uint64_t rng[2], rtw_oracle_vertex* vertices, int32_t capacity,
+                            int32_t* count, float color[3]);
+/* ... for n rays: packed (n, 3), (n, 3), (n,), states (n, 2) in/out, vertices (n, capacity), counts (n,),
+ * colors (n, 3). */
+RTW_API int rtw_oracle_paths(const rtw_world* w, const float* origins, const float* dirs, const float* times,
+                             int64_t n, int32_t max_depth, uint64_t* rng_states, rtw_oracle_vertex* vertices,
+                             int32_t capacity, int32_t* counts, float* colors);
+/* rtw_oracle_ray_color for n rays (Default mode), states in/out. */
+RTW_API int rtw_oracle_ray_colors(const rtw_world* w, const float* origins, const float* dirs, const float* times,
+                                  int64_t n, int32_t max_depth, uint64_t* rng_states, float* colors);
+
 /* One ctr-mode camera sample's radiance: pixel (x, y), global sample index s. */
 RTW_API int rtw_oracle_sample_color(const rtw_world* w, const rtw_render_params* p, int32_t x, int32_t y,
                                     uint32_t s, float color[3]);
