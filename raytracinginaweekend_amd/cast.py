@@ -49,6 +49,12 @@ class CastResult:
         return int(self.t.shape[0])
 
 
+def _cast_result(hits, ints, albedo) -> CastResult:
+    """The (n, HIT_WORDS) float32 records (an array or a device tensor) and their int32 view as a CastResult."""
+    return CastResult(hit=ints[:, 1] >= 0, t=hits[:, 0], leaf=ints[:, 1], position=hits[:, 2:5], normal=hits[:, 5:8],
+                      uv=hits[:, 8:10], front_face=ints[:, 10] != 0, material=ints[:, 11], albedo=albedo)
+
+
 def _is_tensor(a) -> bool:
     return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
 
@@ -238,9 +244,7 @@ class RayCaster:
         if n:  # (an empty tensor has no storage to point at)
             check(lib().rtw_cast_device(self._handle(), C.byref(p), C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr()),
                                         C.c_void_p(alb.data_ptr()) if albedo else None, C.c_void_p(self._stream() or 0)))
-        ints = hits.view(torch.int32)
-        return CastResult(hit=ints[:, 1] >= 0, t=hits[:, 0], leaf=ints[:, 1], position=hits[:, 2:5], normal=hits[:, 5:8],
-                          uv=hits[:, 8:10], front_face=ints[:, 10] != 0, material=ints[:, 11], albedo=alb)
+        return _cast_result(hits, hits.view(torch.int32), alb)
 
     def occluded_device(self, origins, directions, times=None, t_end=None, *, t_start: float = 0.001,
                         seed: int = DEFAULT_SEED, stream: int = 0, albedo: bool = False):
@@ -273,9 +277,7 @@ class RayCaster:
         alb = np.zeros((n, 3), np.float32) if albedo else None
         check(lib().rtw_cast(self._handle(), C.byref(p), C.c_void_p(rays.ctypes.data), n, C.c_void_p(hits.ctypes.data),
                              C.c_void_p(alb.ctypes.data) if albedo else None))
-        ints = hits.view(np.int32)
-        return CastResult(hit=ints[:, 1] >= 0, t=hits[:, 0], leaf=ints[:, 1], position=hits[:, 2:5], normal=hits[:, 5:8],
-                          uv=hits[:, 8:10], front_face=ints[:, 10] != 0, material=ints[:, 11], albedo=alb)
+        return _cast_result(hits, hits.view(np.int32), alb)
 
     def occluded(self, origins, directions, times=None, t_end=None, *, t_start: float = 0.001, seed: int = DEFAULT_SEED,
                  stream: int = 0, albedo: bool = False):

@@ -3799,13 +3799,43 @@ __global__ void encode_kernel(const float* img, int64_t n, uint8_t* out) {
 // then the closest hit over [0.001, inf) with the stream carried on (volume leaves draw from it).  The walk is
 // the reference's (hittable.rs:429-473): depth first over node_a / node_b, the near child by dir[axis] > 0,
 // t_end narrowed by every hit, node_pass (hit_cond AND the proximity cull, which changes no result) -- so the
-// hit is the reference's, ties included.  Every leaf and texture kind reads global memory (ShadeTabs with all
-// offsets -1, as the self-test kernels).  The per-lane stack is the block's dynamic LDS: `depth` entries per
-// lane, the reference tree's depth (upload refuses trees deeper than RTW_STACK).
+// hit is the reference's, ties included.  Every leaf and texture kind reads global memory (kGlobalTabs).
+// The per-lane stack is the block's dynamic LDS: `depth` entries per lane, the reference tree's depth (upload
+// refuses trees deeper than RTW_STACK).
 // The sums are SoA planes in slot order (slot = tile * 64 + lane): a wave stores 256 contiguous bytes per plane.
 // (Measured and dropped, profiles/LOG.md round 11: lanes that start their next sample while the wave's other rays
 // go on, the tree in LDS, node steps at a faster cadence than leaf steps.  None beat this loop.)
+// (Measured and dropped, profiles/LOG.md round 26: this walk, cast_kernel's and radiance_kernel's as one
+// __forceinline__ function.  Same bits; this kernel and radiance_kernel then take one VGPR less and run 1.5-2.4 %
+// slower, whichever way the range, the hit and the stream are passed.  A change to the walk is made in all three.)
 #define RTW_AOV_BLOCK 256
+
+// the tables of the kernels below (first-hit AOVs, ray queries, radiance queries): all offsets -1, every leaf and
+// texture kind reads global memory, as in the self-test kernels
+constexpr ShadeTabs kGlobalTabs{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
+
+// The albedo AOV at a first hit: the material's texture there, through the radiance of its emissive twin, 0 + 1 *
+// texture (rendering.rs:62 on a DiffuseLight); white on a dielectric.
+__device__ __forceinline__ V3 first_hit_albedo(const DWorld& w, const ShadeTabs& S, const Hit& h, Stats& st) {
+    const int4 M = w.materials[h.material];
+    if ((M.x & (RTW_DMAT_IMAGE - 1)) == RTW_MAT_DIELECTRIC) return v3(1.0f, 1.0f, 1.0f);
+    const V3 tc = (M.x & RTW_DMAT_IMAGE) != 0
+                      ? image_texel<false>(w, M.z, (int32_t)((uint32_t)M.w >> 16), M.w & 0xFFFF, h, st)
+                      : texture_sample<false, TX_ANY>(w, M.y, h, st, S);
+    return add(v3(0.0f, 0.0f, 0.0f), conv(v3(1.0f, 1.0f, 1.0f), tc));
+}
+
+// A caller's ray (rtw_ray): two 16-byte loads, {origin, time} and {direction, t_end}.
+__device__ __forceinline__ Ray load_query_ray(const float4* rays, uint32_t i, float& t_end) {
+    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+    Ray ray;
+    ray.o = v3(r0.x, r0.y, r0.z);
+    ray.time = r0.w;
+    ray.d = v3(r1.x, r1.y, r1.z);
+    t_end = r1.w;
+    return ray;
+}
+
 struct AovArgs {
     DWorld w;
     int32_t width, height, tiles_x;
@@ -3856,7 +3886,7 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void aov_kernel(AovArgs A) {
     if (!aov_slot_pixel(PART ? (tile << 6) | (slot & 63u) : slot, A.tiles_x, A.width, A.height, px, py)) return;  // (no barrier below)
     const uint32_t pix = (uint32_t)(py * A.width + px);
     const float fx = (float)px * A.sx, fy = (float)py * A.sy;
-    const ShadeTabs S{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
+    const ShadeTabs S = kGlobalTabs;
     int32_t* stack = reinterpret_cast<int32_t*>(smem) + threadIdx.x;
     Stats st;
     // (a fresh accumulator's planes hold +0: the first add starts from them too)
@@ -3955,16 +3985,7 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void aov_kernel(AovArgs A) {
             nv = mul(add(h.n, v3(1.0f, 1.0f, 1.0f)), 0.5f);  // rendering.rs:110-113
             dsum = dsum + te;
             hits += 1u;
-            if (A.albedo) {
-                const int4 M = w.materials[h.material];
-                if ((M.x & (RTW_DMAT_IMAGE - 1)) != RTW_MAT_DIELECTRIC) {
-                    const V3 tc = (M.x & RTW_DMAT_IMAGE) != 0
-                                      ? image_texel<false>(w, M.z, (int32_t)((uint32_t)M.w >> 16), M.w & 0xFFFF, h, st)
-                                      : texture_sample<false, TX_ANY>(w, M.y, h, st, S);
-                    // the radiance of the emissive twin: 0 + 1 * texture (rendering.rs:62 on a DiffuseLight)
-                    a = add(v3(0.0f, 0.0f, 0.0f), conv(v3(1.0f, 1.0f, 1.0f), tc));
-                }
-            }
+            if (A.albedo) a = first_hit_albedo(w, S, h, st);
         } else {
             // RTW_MODE_NORMALS on a miss: the primary ray's background, through shade()'s expression
             nv = add(v3(0.0f, 0.0f, 0.0f), conv(v3(1.0f, 1.0f, 1.0f), background(w.wc->bg, dot(v3(0.0f, 1.0f, 0.0f), ray.d))));
@@ -4035,19 +4056,15 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void cast_kernel(CastArgs A) {
     const DWorld& w = A.w;
     const uint32_t i = blockIdx.x * RTW_AOV_BLOCK + threadIdx.x;  // (the grid is ceil(n / 256) <= 2^23 blocks)
     if (i >= A.n) return;  // (no barrier below)
-    const float4 r0 = A.rays[2 * (size_t)i], r1 = A.rays[2 * (size_t)i + 1];
-    Ray ray;
-    ray.o = v3(r0.x, r0.y, r0.z);
-    ray.time = r0.w;
-    ray.d = v3(r1.x, r1.y, r1.z);
+    float te;  // the ray's own t_end
+    const Ray ray = load_query_ray(A.rays, i, te);
     const float ts = A.t_start;
-    const ShadeTabs S{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
+    const ShadeTabs S = kGlobalTabs;
     int32_t* stack = reinterpret_cast<int32_t*>(smem) + threadIdx.x;
     Stats st;
     rtw_xoro rng = rtw_sample_stream(A.seed_key, i, A.stream);
     const RayPre rp = ray_pre(ray, A.mk_world != 0);
     const uint32_t sgn = (ray.d.x > 0.0f ? 1u : 0u) | (ray.d.y > 0.0f ? 2u : 0u) | (ray.d.z > 0.0f ? 4u : 0u);
-    float te = r1.w;
     int32_t found = -1, node = w.root, sp = 0;
     bool live = true;
     while (live) {
@@ -4102,15 +4119,7 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void cast_kernel(CastArgs A) {
         h0 = make_float4(te, __int_as_float(found), h.pos.x, h.pos.y);
         h1 = make_float4(h.pos.z, h.n.x, h.n.y, h.n.z);
         h2 = make_float4(h.u, h.v, __int_as_float(h.front ? 1 : 0), __int_as_float(h.material));
-        if (ALBEDO) {  // aov_kernel's value
-            const int4 M = w.materials[h.material];
-            if ((M.x & (RTW_DMAT_IMAGE - 1)) != RTW_MAT_DIELECTRIC) {
-                const V3 tc = (M.x & RTW_DMAT_IMAGE) != 0
-                                  ? image_texel<false>(w, M.z, (int32_t)((uint32_t)M.w >> 16), M.w & 0xFFFF, h, st)
-                                  : texture_sample<false, TX_ANY>(w, M.y, h, st, S);
-                a = add(v3(0.0f, 0.0f, 0.0f), conv(v3(1.0f, 1.0f, 1.0f), tc));
-            }
-        }
+        if (ALBEDO) a = first_hit_albedo(w, S, h, st);  // aov_kernel's value
     }
     float4* out = A.hits + 3 * (size_t)i;
     out[0] = h0;
@@ -4164,7 +4173,7 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void radiance_kernel(RadArgs A) {
         (int32_t)((blockIdx.x * (RTW_AOV_BLOCK / 64) + (threadIdx.x >> 6)) * (uint32_t)RTW_RAD_ITEMS));
     if (cursor >= A.items) return;  // wave-uniform (no barrier below)
     const uint32_t end = min(cursor + (uint32_t)RTW_RAD_ITEMS, A.items);
-    const ShadeTabs S{-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 0};
+    const ShadeTabs S = kGlobalTabs;
     int32_t* stack = reinterpret_cast<int32_t*>(smem) + threadIdx.x;
     Stats st;
     Path P;
@@ -4190,10 +4199,8 @@ __global__ __launch_bounds__(RTW_AOV_BLOCK) void radiance_kernel(RadArgs A) {
                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
                 if (j < end) {
                     const uint32_t i = j / A.samples, k = j - i * A.samples;
-                    const float4 r0 = A.rays[2 * (size_t)i], r1 = A.rays[2 * (size_t)i + 1];
-                    P.ray.o = v3(r0.x, r0.y, r0.z);
-                    P.ray.time = r0.w;
-                    P.ray.d = v3(r1.x, r1.y, r1.z);
+                    float t_end;  // (not read: every segment searches [0.001, +inf))
+                    P.ray = load_query_ray(A.rays, i, t_end);
                     P.att = v3(1.0f, 1.0f, 1.0f);
                     P.acc = v3(0.0f, 0.0f, 0.0f);
                     P.depth = A.max_depth;
@@ -6952,6 +6959,10 @@ static void aov_orphan(rtw_aov* a) {
     a->g = nullptr;
 }
 
+// the reference-tree stack of a 256-lane block (the AOV add, the ray queries, the radiance queries): one int32_t per level
+// of the reference tree and lane (g->depth >= that tree's depth, <= RTW_STACK)
+static size_t ref_stack_lds(const rtw_gpu_world* g) { return (size_t)std::max(1, g->depth) * RTW_AOV_BLOCK * sizeof(int32_t); }
+
 static int aov_create_part(rtw_gpu_world* g, const rtw_render_params* p, uint32_t channels, int32_t part_index,
                            int32_t part_count, rtw_aov** out);
 
@@ -7139,8 +7150,7 @@ extern "C" RTW_API int rtw_aov_add(rtw_aov* a, uint32_t n, void* stream) {
     A.pl_cap = a->pl_cap;
     A.part_index = a->part_index;
     A.part_count = a->part_count;
-    // the stack: one int32_t per level of the reference tree and lane (g->depth >= that tree's depth, <= RTW_STACK)
-    const size_t lds = (size_t)std::max(1, g->depth) * RTW_AOV_BLOCK * sizeof(int32_t);
+    const size_t lds = ref_stack_lds(g);
     const dim3 grid((a->slots + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK), block(RTW_AOV_BLOCK);
     hipStream_t s = (hipStream_t)stream;
     if (a->slots == 0) {  // a part without tiles: nothing to trace, and the count goes on as the group's does
@@ -7231,8 +7241,6 @@ CastArgs cast_args(const rtw_gpu_world* g, const rtw_cast_params* p, const rtw_r
     A.seed_key = rtw_seed_key(p->seed);
     return A;
 }
-// the stack: one int32_t per level of the reference tree and lane, as rtw_aov_add's
-size_t cast_lds(const rtw_gpu_world* g) { return (size_t)std::max(1, g->depth) * RTW_AOV_BLOCK * sizeof(int32_t); }
 }  // namespace
 
 extern "C" RTW_API int rtw_cast_device(rtw_gpu_world* g, const rtw_cast_params* p, const rtw_ray* d_rays, int64_t n,
@@ -7245,8 +7253,8 @@ extern "C" RTW_API int rtw_cast_device(rtw_gpu_world* g, const rtw_cast_params* 
     A.hits = reinterpret_cast<float4*>(d_hits);
     A.albedo = d_albedo;
     const dim3 grid((unsigned)((n + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK)), block(RTW_AOV_BLOCK);
-    if (d_albedo) hipLaunchKernelGGL((cast_kernel<false, true>), grid, block, cast_lds(g), (hipStream_t)stream, A);
-    else hipLaunchKernelGGL((cast_kernel<false, false>), grid, block, cast_lds(g), (hipStream_t)stream, A);
+    if (d_albedo) hipLaunchKernelGGL((cast_kernel<false, true>), grid, block, ref_stack_lds(g), (hipStream_t)stream, A);
+    else hipLaunchKernelGGL((cast_kernel<false, false>), grid, block, ref_stack_lds(g), (hipStream_t)stream, A);
     HIP_TRY(hipGetLastError());
     return RTW_OK;
 }
@@ -7260,7 +7268,7 @@ extern "C" RTW_API int rtw_occluded_device(rtw_gpu_world* g, const rtw_cast_para
     CastArgs A = cast_args(g, p, d_rays, n);
     A.any = d_out;
     const dim3 grid((unsigned)((n + RTW_AOV_BLOCK - 1) / RTW_AOV_BLOCK)), block(RTW_AOV_BLOCK);
-    hipLaunchKernelGGL((cast_kernel<true, false>), grid, block, cast_lds(g), (hipStream_t)stream, A);
+    hipLaunchKernelGGL((cast_kernel<true, false>), grid, block, ref_stack_lds(g), (hipStream_t)stream, A);
     HIP_TRY(hipGetLastError());
     return RTW_OK;
 }
@@ -7377,7 +7385,7 @@ extern "C" RTW_API int rtw_radiance_samples_device(rtw_gpu_world* g, const rtw_r
     A.seed_key = rtw_seed_key(p->seed);
     constexpr uint32_t per_block = (RTW_AOV_BLOCK / 64) * RTW_RAD_ITEMS;
     const dim3 grid((A.items + per_block - 1) / per_block), block(RTW_AOV_BLOCK);
-    hipLaunchKernelGGL(radiance_kernel, grid, block, cast_lds(g), (hipStream_t)stream, A);
+    hipLaunchKernelGGL(radiance_kernel, grid, block, ref_stack_lds(g), (hipStream_t)stream, A);
     HIP_TRY(hipGetLastError());
     return RTW_OK;
 }
